@@ -15,6 +15,14 @@ Launch (the driver's contract):
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line. ``--dump-outputs DIR`` additionally writes what the last timed step
+produced (``eps.npy``: the gathered noise prediction, ``x.npy``: the latent
+after the sampler update) so two builds can be compared output for output;
+inputs and weights are seeded, so equal arguments give equal inputs.
+``--full`` is reserved for secondary measurements that need runs of their
+own; none exist today, so it currently adds nothing to a plain run.
 """
 from __future__ import annotations
 
@@ -60,11 +68,40 @@ def parse_args(argv=None):
                     help="comma-separated per-rank split weights (e.g. 60,40 "
                          "for the Z-Image headline config); default even")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's "
+                         "outputs (noise prediction + updated latent) as "
+                         "DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement/check; the "
+                         "benchmark has none beyond the headline loop today, "
+                         "so this currently adds nothing")
     return ap.parse_args(argv)
 
 
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16,
           "fp32": torch.float32, "fp8": torch.bfloat16}
+
+
+DUMP_BUDGET_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir, tensors):
+    """Write each tensor as out_dir/<name>.npy in float32. Arrays that would
+    push the directory past DUMP_BUDGET_BYTES are cut down to a fixed,
+    seeded sample of their flattened elements (same indices every run)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    tensors = {k: v for k, v in tensors.items() if v is not None}
+    per_array = DUMP_BUDGET_BYTES // max(1, len(tensors)) - 4096  # .npy header
+    for name, ten in tensors.items():
+        flat = ten.detach().to("cpu", torch.float32).contiguous()
+        if flat.numel() * 4 > per_array:
+            g = torch.Generator(device="cpu").manual_seed(20240607)
+            idx = torch.randperm(flat.numel(), generator=g)[: per_array // 4]
+            flat = flat.reshape(-1)[idx.sort().values]
+        np.save(os.path.join(out_dir, f"{name}.npy"), flat.numpy())
 
 
 def main(argv=None):
@@ -164,6 +201,8 @@ def main(argv=None):
             out = model(sx, st_, context=my_ctx, **my_kw)
         graph_state.update({"graph": g, "x": sx, "t": st_, "out": out})
 
+    last = {}
+
     @torch.no_grad()
     def step(i: int) -> None:
         my_x = scatterv(x if info.is_lead else None, sizes, info, template=x)
@@ -171,6 +210,7 @@ def main(argv=None):
         eps = run_model(my_x, my_t)
         out = gatherv(eps, sizes, info, dst=0)
         if info.is_lead:
+            last["eps"] = out  # reference only; read after the timed loop
             # sampler update on the lead (Euler-style), keeps x live
             x.sub_(0.01 * out.to(x.dtype))
 
@@ -201,8 +241,8 @@ def main(argv=None):
 
     result = None
     if info.is_lead:
-        sec_per_it = dt / args.steps
-        images_per_s = args.batch * args.steps / dt
+        sec_per_it = dt / max(1, args.steps)
+        images_per_s = args.batch * args.steps / dt if dt > 0 else 0.0
         result = {
             "metric": "images_per_s (whole-job; sec/it in ms_per_step), "
                       f"{args.model} {args.px}^2 batch={args.batch}",
@@ -248,6 +288,8 @@ def main(argv=None):
         # deterministic end-state fingerprint: lets the world-N gloo tests
         # assert N-rank scatter/forward/gather == single-process math
         result["x_checksum"] = round(float(x.float().abs().mean()), 8)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"eps": last.get("eps"), "x": x})
         line = json.dumps(result)
         print(line)
         if args.json_out:
