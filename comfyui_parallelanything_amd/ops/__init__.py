@@ -33,6 +33,8 @@ _EXT = None
 _EXT_TRIED = False
 _ALLOW_EAGER = os.environ.get("PA_ALLOW_EAGER", "0") == "1"
 _WARNED: set = set()
+# 16-bit element types with native instantiations of every kernel below
+_NATIVE16 = (torch.bfloat16, torch.float16)
 
 
 def _load_ext():
@@ -167,7 +169,7 @@ def attention(q, k, v, scale: Optional[float] = None) -> torch.Tensor:
         ext = _require_ext("attn_fwd")
         if ext is not None:
             D = q.shape[-1]
-            if q.dtype == torch.bfloat16 and D in (64, 128):
+            if q.dtype in _NATIVE16 and D in (64, 128):
                 return ext.attn_fwd(q.contiguous(), k.contiguous(),
                                     v.contiguous(), float(scale))
             _unsupported("attn_fwd", f"dtype={q.dtype}, D={D}")
@@ -198,9 +200,9 @@ def attention_bshd(q, k, v, scale: Optional[float] = None) -> torch.Tensor:
         ext = _require_ext("attn_fwd_bshd")
         if ext is not None:
             D = q.shape[-1]
-            if q.dtype == torch.bfloat16 and D in (64, 128):
+            if q.dtype in _NATIVE16 and D in (64, 128):
                 return ext.attn_fwd_bshd(q, k, v, float(scale))
-            if q.dtype == torch.bfloat16 and D < 128:
+            if q.dtype in _NATIVE16 and D < 128:
                 Dp = 64 if D <= 64 else 128
                 pad = (0, Dp - D)
                 out = ext.attn_fwd_bshd(
@@ -232,12 +234,17 @@ def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None):
             out = attention_bshd(q, k, v, scale)
             return out[:, :split].contiguous(), out[:, split:].contiguous()
         ext = _require_ext("attn_fwd_bshd_split")
-        if ext is not None and q.dtype == torch.bfloat16 \
+        if ext is not None and q.dtype in _NATIVE16 \
                 and q.shape[-1] in (64, 128):
             a, b = ext.attn_fwd_bshd_split(q, k, v, float(scale), int(split))
             return a, b
-        _unsupported("attn_fwd_bshd_split",
-                     f"dtype={q.dtype}, D={q.shape[-1]}")
+        # 16-bit head dims below 128 still run the native kernel through
+        # attention_bshd's zero-pad route (only the split epilogue is
+        # composed from slices) — that is no reference-path fallback
+        if not (ext is not None and q.dtype in _NATIVE16
+                and q.shape[-1] < 128):
+            _unsupported("attn_fwd_bshd_split",
+                         f"dtype={q.dtype}, D={q.shape[-1]}")
     out = attention_bshd(q, k, v, scale)
     return out[:, :split].contiguous(), out[:, split:].contiguous()
 
@@ -250,7 +257,7 @@ def qk_norm_rope_(q, k, wq, wk, cs, eps: float = 1e-6):
     """
     if q.is_cuda:
         ext = _require_ext("qk_norm_rope_")
-        if ext is not None and q.dtype == torch.bfloat16 and q.shape[-1] <= 128:
+        if ext is not None and q.dtype in _NATIVE16 and q.shape[-1] <= 128:
             ext.qk_norm_rope_(q, k, wq, wk, cs, eps)
             return q, k
         _unsupported("qk_norm_rope_", f"dtype={q.dtype}, D={q.shape[-1]}")
@@ -267,7 +274,8 @@ def pack_joint_qkv(txt_qkv, img_qkv, wq_t, wk_t, wq_i, wk_i, cs,
     [B, T+Si, H, D] q/k/v in one pass (txt_qkv/img_qkv: [B,S,3,H,D] views)."""
     if txt_qkv.is_cuda:
         ext = _require_ext("pack_joint_qkv")
-        if ext is not None and txt_qkv.dtype == torch.bfloat16                 and txt_qkv.shape[-1] <= 128:
+        if ext is not None and txt_qkv.dtype in _NATIVE16 \
+                and txt_qkv.shape[-1] <= 128:
             return ext.pack_joint_qkv(txt_qkv, img_qkv, wq_t, wk_t, wq_i, wk_i,
                                       cs, eps)
         _unsupported("pack_joint_qkv",

@@ -37,6 +37,58 @@ PA_DEV float bf2f(bf16 v) { return __bfloat162float(v); }
 PA_DEV bf16 f2bf(float v) { return __float2bfloat16(v); }
 
 // ---------------------------------------------------------------------------
+// 16-bit element trait: bf16 and fp16 share every vector width, LDS layout
+// and lane shuffle (short8 / uint stay the storage types); only the
+// conversions and the MFMA opcode differ.
+//   ld / st : raw 16-bit lane <-> float (st rounds to nearest even)
+//   pack2   : two floats -> one packed 32-bit word (lo in bits 0..15)
+//   mfma32  : v_mfma_f32_32x32x16_{bf16,f16}
+// The build defines __HIP_NO_HALF_OPERATORS__/__HIP_NO_HALF_CONVERSIONS__, so
+// fp16 is the native _Float16, never __half.
+// ---------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(8))) _Float16 half8;
+typedef __attribute__((ext_vector_type(2))) _Float16 half2v;
+
+template <typename E> struct Elem16;
+
+template <> struct Elem16<bf16> {
+    static PA_DEV float ld(unsigned short u) {
+        return bf2f(__ushort_as_bfloat16(u));
+    }
+    static PA_DEV unsigned short st(float f) {
+        return __bfloat16_as_ushort(f2bf(f));
+    }
+    static PA_DEV unsigned int pack2(float lo, float hi) {
+        unsigned int r;
+        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+        return r;
+    }
+    static PA_DEV f32x16 mfma32(short8 a, short8 b, f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    }
+};
+
+template <> struct Elem16<_Float16> {
+    static PA_DEV float ld(unsigned short u) {
+        return (float)__builtin_bit_cast(_Float16, u);
+    }
+    static PA_DEV unsigned short st(float f) {
+        return __builtin_bit_cast(unsigned short, (_Float16)f);
+    }
+    static PA_DEV unsigned int pack2(float lo, float hi) {
+        // one v_cvt_pk_f16_f32 (RNE) — not the round-toward-zero cvt_pkrtz
+        return __builtin_bit_cast(
+            unsigned int, __builtin_convertvector(f32x2{lo, hi}, half2v));
+    }
+    static PA_DEV f32x16 mfma32(short8 a, short8 b, f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(
+            __builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c,
+            0, 0, 0);
+    }
+};
+
+// ---------------------------------------------------------------------------
 // Wave/block reductions (wave64; lane groups via __shfl_xor over 64 lanes).
 // ---------------------------------------------------------------------------
 PA_DEV float wave_reduce_sum(float v) {
@@ -86,10 +138,12 @@ __global__ void rms_norm_kernel(const T* __restrict__ x, const T* __restrict__ w
     }
 }
 
-// bf16 fast path: 8-wide vector loads/stores.
-__global__ void rms_norm_bf16_kernel(const bf16* __restrict__ x,
-                                     const bf16* __restrict__ w,
-                                     bf16* __restrict__ out, int D, float eps) {
+// 16-bit fast path (E = bf16 | _Float16): 8-wide vector loads/stores.
+template <typename E>
+__global__ void rms_norm_vec_kernel(const E* __restrict__ x,
+                                    const E* __restrict__ w,
+                                    E* __restrict__ out, int D, float eps) {
+    using EL = Elem16<E>;
     const long row = blockIdx.x;
     const short8* xr = reinterpret_cast<const short8*>(x + row * (long)D);
     short8* yr = reinterpret_cast<short8*>(out + row * (long)D);
@@ -102,7 +156,7 @@ __global__ void rms_norm_bf16_kernel(const bf16* __restrict__ x,
         short8 v = xr[i];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            float f = bf2f(__ushort_as_bfloat16((unsigned short)v[j]));
+            float f = EL::ld((unsigned short)v[j]);
             acc += f * f;
         }
     }
@@ -115,15 +169,15 @@ __global__ void rms_norm_bf16_kernel(const bf16* __restrict__ x,
             short8 wv8 = wv[i];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                float f = bf2f(__ushort_as_bfloat16((unsigned short)v[j])) * rrms *
-                          bf2f(__ushort_as_bfloat16((unsigned short)wv8[j]));
-                o[j] = (short)__bfloat16_as_ushort(f2bf(f));
+                float f = EL::ld((unsigned short)v[j]) * rrms *
+                          EL::ld((unsigned short)wv8[j]);
+                o[j] = (short)EL::st(f);
             }
         } else {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                float f = bf2f(__ushort_as_bfloat16((unsigned short)v[j])) * rrms;
-                o[j] = (short)__bfloat16_as_ushort(f2bf(f));
+                float f = EL::ld((unsigned short)v[j]) * rrms;
+                o[j] = (short)EL::st(f);
             }
         }
         yr[i] = o;
@@ -131,11 +185,13 @@ __global__ void rms_norm_bf16_kernel(const bf16* __restrict__ x,
 }
 
 // Small-D fast path (qk-norm: D = head_dim 64..256): one WAVE per row, four
-// rows per 256-thread block; pair loads (uint = 2 bf16) when D % 128 == 0.
-__global__ void rms_norm_bf16_row_kernel(const bf16* __restrict__ x,
-                                         const bf16* __restrict__ w,
-                                         bf16* __restrict__ out,
-                                         long rows, int D, float eps) {
+// rows per 256-thread block; pair loads (uint = 2 elements) when D % 128 == 0.
+template <typename E>
+__global__ void rms_norm_row_kernel(const E* __restrict__ x,
+                                    const E* __restrict__ w,
+                                    E* __restrict__ out,
+                                    long rows, int D, float eps) {
+    using EL = Elem16<E>;
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -150,24 +206,23 @@ __global__ void rms_norm_bf16_row_kernel(const bf16* __restrict__ x,
     for (int i = 0; i < n; ++i) {
         unsigned int u = xr[lane + i * 64];
         vals[i] = u;
-        float a = bf2f(__ushort_as_bfloat16((unsigned short)(u & 0xffff)));
-        float b = bf2f(__ushort_as_bfloat16((unsigned short)(u >> 16)));
+        float a = EL::ld((unsigned short)(u & 0xffff));
+        float b = EL::ld((unsigned short)(u >> 16));
         acc += a * a + b * b;
     }
     acc = wave_reduce_sum(acc);
     const float rrms = rsqrtf(acc / (float)D + eps);
     for (int i = 0; i < n; ++i) {
         unsigned int u = vals[i];
-        float a = bf2f(__ushort_as_bfloat16((unsigned short)(u & 0xffff))) * rrms;
-        float b = bf2f(__ushort_as_bfloat16((unsigned short)(u >> 16))) * rrms;
+        float a = EL::ld((unsigned short)(u & 0xffff)) * rrms;
+        float b = EL::ld((unsigned short)(u >> 16)) * rrms;
         if (w != nullptr) {
             unsigned int uw = wr[lane + i * 64];
-            a *= bf2f(__ushort_as_bfloat16((unsigned short)(uw & 0xffff)));
-            b *= bf2f(__ushort_as_bfloat16((unsigned short)(uw >> 16)));
+            a *= EL::ld((unsigned short)(uw & 0xffff));
+            b *= EL::ld((unsigned short)(uw >> 16));
         }
         yr[lane + i * 64] =
-            (unsigned int)__bfloat16_as_ushort(f2bf(a)) |
-            ((unsigned int)__bfloat16_as_ushort(f2bf(b)) << 16);
+            (unsigned int)EL::st(a) | ((unsigned int)EL::st(b) << 16);
     }
 }
 
@@ -224,12 +279,14 @@ __global__ void gate_residual_kernel(const T* __restrict__ res,
 }
 
 
-// bf16 fast path: short8 vector loads both passes (mean/var re-read hits L2)
-__global__ void layer_norm_mod_bf16_kernel(const bf16* __restrict__ x,
-                                           const bf16* __restrict__ scale,
-                                           const bf16* __restrict__ shift,
-                                           bf16* __restrict__ out,
-                                           int S, int D, float eps) {
+// 16-bit fast path: short8 vector loads both passes (mean/var re-read hits L2)
+template <typename E>
+__global__ void layer_norm_mod_vec_kernel(const E* __restrict__ x,
+                                          const E* __restrict__ scale,
+                                          const E* __restrict__ shift,
+                                          E* __restrict__ out,
+                                          int S, int D, float eps) {
+    using EL = Elem16<E>;
     const long row = blockIdx.x;
     const long b = row / S;
     const short8* xr = reinterpret_cast<const short8*>(x + row * (long)D);
@@ -244,7 +301,7 @@ __global__ void layer_norm_mod_bf16_kernel(const bf16* __restrict__ x,
         short8 v = xr[i];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            float f = bf2f(__ushort_as_bfloat16((unsigned short)v[j]));
+            float f = EL::ld((unsigned short)v[j]);
             s1 += f;
             s2 += f * f;
         }
@@ -256,10 +313,10 @@ __global__ void layer_norm_mod_bf16_kernel(const bf16* __restrict__ x,
         short8 v = xr[i], a = sc[i], c = sh[i], o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            float f = (bf2f(__ushort_as_bfloat16((unsigned short)v[j])) - mean) * rstd;
-            f = f * (1.f + bf2f(__ushort_as_bfloat16((unsigned short)a[j]))) +
-                bf2f(__ushort_as_bfloat16((unsigned short)c[j]));
-            o[j] = (short)__bfloat16_as_ushort(f2bf(f));
+            float f = (EL::ld((unsigned short)v[j]) - mean) * rstd;
+            f = f * (1.f + EL::ld((unsigned short)a[j])) +
+                EL::ld((unsigned short)c[j]);
+            o[j] = (short)EL::st(f);
         }
         yr[i] = o;
     }
@@ -351,12 +408,14 @@ __global__ void layer_norm_mod_fp8_kernel(
     (void)s_entry;
 }
 
-// bf16 fast path: 8-wide gated residual
-__global__ void gate_residual_bf16_kernel(const bf16* __restrict__ res,
-                                          const bf16* __restrict__ gate,
-                                          const bf16* __restrict__ x,
-                                          bf16* __restrict__ out,
-                                          long total8, int S, int DV) {
+// 16-bit fast path: 8-wide gated residual
+template <typename E>
+__global__ void gate_residual_vec_kernel(const E* __restrict__ res,
+                                         const E* __restrict__ gate,
+                                         const E* __restrict__ x,
+                                         E* __restrict__ out,
+                                         long total8, int S, int DV) {
+    using EL = Elem16<E>;
     const long stride = (long)gridDim.x * blockDim.x;
     const short8* rv = reinterpret_cast<const short8*>(res);
     const short8* gv = reinterpret_cast<const short8*>(gate);
@@ -369,10 +428,10 @@ __global__ void gate_residual_bf16_kernel(const bf16* __restrict__ res,
         short8 r = rv[i], g = gv[b * DV + dv], xx = xv[i], o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            float f = bf2f(__ushort_as_bfloat16((unsigned short)r[j])) +
-                      bf2f(__ushort_as_bfloat16((unsigned short)g[j])) *
-                          bf2f(__ushort_as_bfloat16((unsigned short)xx[j]));
-            o[j] = (short)__bfloat16_as_ushort(f2bf(f));
+            float f = EL::ld((unsigned short)r[j]) +
+                      EL::ld((unsigned short)g[j]) *
+                          EL::ld((unsigned short)xx[j]);
+            o[j] = (short)EL::st(f);
         }
         ov[i] = o;
     }
@@ -457,9 +516,11 @@ __global__ void gelu_fp8_kernel(const bf16* __restrict__ x,
 }
 
 
-__global__ void gelu_tanh_bf16_kernel(const bf16* __restrict__ x,
-                                      bf16* __restrict__ out, long total8,
-                                      long rows, long w8, long in_stride8) {
+template <typename E>
+__global__ void gelu_tanh_vec_kernel(const E* __restrict__ x,
+                                     E* __restrict__ out, long total8,
+                                     long rows, long w8, long in_stride8) {
+    using EL = Elem16<E>;
     // strided rows supported (last-dim slices of a fused projection read in
     // place — no .contiguous() copy); output is written dense.
     const long stride = (long)gridDim.x * blockDim.x;
@@ -472,7 +533,7 @@ __global__ void gelu_tanh_bf16_kernel(const bf16* __restrict__ x,
         short8 v = xv[src], o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float f = bf2f(__ushort_as_bfloat16((unsigned short)v[j]));
+            const float f = EL::ld((unsigned short)v[j]);
             const float c = 0.7978845608028654f * (f + 0.044715f * f * f * f);
             // tanh via the HARDWARE exp2 (v_exp_f32): libm tanhf measured
             // only 2.7 TB/s on this pass (rocprof r02 fp8 mix). Negative-
@@ -484,7 +545,7 @@ __global__ void gelu_tanh_bf16_kernel(const bf16* __restrict__ x,
             // v_rcp_f32 (~1 ulp) instead of the ~10-instr IEEE divide
                 const float r = __builtin_amdgcn_rcpf(1.f + En);
             const float g = f * (c >= 0.f ? r : 1.f - r);
-            o[j] = (short)__bfloat16_as_ushort(f2bf(g));
+            o[j] = (short)EL::st(g);
         }
         ov[i] = o;
     }
@@ -622,14 +683,16 @@ __global__ void ts_embed_mlp_kernel(const float* __restrict__ t,
 // qkv projection output (strided [B, S, H, D] views), replacing four
 // separate bandwidth passes (rms q, rms k, rope q, rope k).
 // ---------------------------------------------------------------------------
-__global__ void qk_norm_rope_kernel(bf16* __restrict__ q, bf16* __restrict__ k,
-                                    const bf16* __restrict__ wq,
-                                    const bf16* __restrict__ wk,
+template <typename E>
+__global__ void qk_norm_rope_kernel(E* __restrict__ q, E* __restrict__ k,
+                                    const E* __restrict__ wq,
+                                    const E* __restrict__ wk,
                                     const float* __restrict__ cs,
                                     int S, int H, int D,
                                     long q_bs, long q_hs, long q_ss,
                                     long k_bs, long k_hs, long k_ss,
                                     long n_rows, float eps) {
+    using EL = Elem16<E>;
     // RPW rows of q AND k per wave with all loads issued before any
     // reduction: 8 independent loads in flight per lane instead of 2
     // (the single-row version measured latency-bound at ~650 GB/s).
@@ -667,16 +730,16 @@ __global__ void qk_norm_rope_kernel(bf16* __restrict__ q, bf16* __restrict__ k,
         cvec[i] = cs[((long)sj * pairs + ln) * 2 + 0];
         svec[i] = cs[((long)sj * pairs + ln) * 2 + 1];
     }
-    const float wq0 = bf2f(__ushort_as_bfloat16((unsigned short)(uwq & 0xffff)));
-    const float wq1 = bf2f(__ushort_as_bfloat16((unsigned short)(uwq >> 16)));
-    const float wk0 = bf2f(__ushort_as_bfloat16((unsigned short)(uwk & 0xffff)));
-    const float wk1 = bf2f(__ushort_as_bfloat16((unsigned short)(uwk >> 16)));
+    const float wq0 = EL::ld((unsigned short)(uwq & 0xffff));
+    const float wq1 = EL::ld((unsigned short)(uwq >> 16));
+    const float wk0 = EL::ld((unsigned short)(uwk & 0xffff));
+    const float wk1 = EL::ld((unsigned short)(uwk >> 16));
 #pragma unroll
     for (int i = 0; i < RPW; ++i) {
         if (wave * RPW + i >= n_rows) break;
         {
-            float a0 = bf2f(__ushort_as_bfloat16((unsigned short)(uq[i] & 0xffff)));
-            float a1 = bf2f(__ushort_as_bfloat16((unsigned short)(uq[i] >> 16)));
+            float a0 = EL::ld((unsigned short)(uq[i] & 0xffff));
+            float a1 = EL::ld((unsigned short)(uq[i] >> 16));
             float ss_ = act ? a0 * a0 + a1 * a1 : 0.f;
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1)
@@ -687,12 +750,12 @@ __global__ void qk_norm_rope_kernel(bf16* __restrict__ q, bf16* __restrict__ k,
             const float o0 = a0 * cvec[i] - a1 * svec[i];
             const float o1 = a0 * svec[i] + a1 * cvec[i];
             if (act)
-                qp[i][lane] = (unsigned int)__bfloat16_as_ushort(f2bf(o0)) |
-                              ((unsigned int)__bfloat16_as_ushort(f2bf(o1)) << 16);
+                qp[i][lane] = (unsigned int)EL::st(o0) |
+                              ((unsigned int)EL::st(o1) << 16);
         }
         {
-            float a0 = bf2f(__ushort_as_bfloat16((unsigned short)(uk[i] & 0xffff)));
-            float a1 = bf2f(__ushort_as_bfloat16((unsigned short)(uk[i] >> 16)));
+            float a0 = EL::ld((unsigned short)(uk[i] & 0xffff));
+            float a1 = EL::ld((unsigned short)(uk[i] >> 16));
             float ss_ = act ? a0 * a0 + a1 * a1 : 0.f;
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1)
@@ -703,8 +766,8 @@ __global__ void qk_norm_rope_kernel(bf16* __restrict__ q, bf16* __restrict__ k,
             const float o0 = a0 * cvec[i] - a1 * svec[i];
             const float o1 = a0 * svec[i] + a1 * cvec[i];
             if (act)
-                kp[i][lane] = (unsigned int)__bfloat16_as_ushort(f2bf(o0)) |
-                              ((unsigned int)__bfloat16_as_ushort(f2bf(o1)) << 16);
+                kp[i][lane] = (unsigned int)EL::st(o0) |
+                              ((unsigned int)EL::st(o1) << 16);
         }
     }
 }
@@ -1074,9 +1137,29 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(
 #define CHECK_GPU(t) TORCH_CHECK((t).is_cuda(), #t " must be on a HIP device")
 #define CHECK_LASTDIM(t) TORCH_CHECK((t).stride(-1) == 1, #t " last dim must be contiguous")
 
+// The kernels take raw pointers: every tensor whose pointer is cast to the
+// element type of `ref` must carry ref's dtype, or an fp16 buffer would be
+// read by a bf16 instantiation (and vice versa).
+#define CHECK_SAME_DTYPE(t, ref)                                              \
+    TORCH_CHECK((t).scalar_type() == (ref).scalar_type(),                     \
+                #t " dtype (", (t).scalar_type(), ") must match " #ref " (",  \
+                (ref).scalar_type(), ")")
+
 static hipStream_t cur_stream() {
     return c10::hip::getCurrentHIPStream().stream();
 }
+
+static bool is_elem16(at::ScalarType t) {
+    return t == at::kBFloat16 || t == at::kHalf;
+}
+
+// Runs the statement(s) with `E` bound to the kernels' element type for a
+// 16-bit scalar type (caller has checked is_elem16).
+#define PA_WITH_ELEM16(ST, ...)                                               \
+    do {                                                                      \
+        if ((ST) == at::kBFloat16) { using E = bf16; __VA_ARGS__; }           \
+        else { using E = _Float16; __VA_ARGS__; }                             \
+    } while (0)
 
 at::Tensor rms_norm(at::Tensor x, std::optional<at::Tensor> w, double eps) {
     CHECK_GPU(x);
@@ -1084,36 +1167,36 @@ at::Tensor rms_norm(at::Tensor x, std::optional<at::Tensor> w, double eps) {
     auto out = at::empty_like(xc);
     const long rows = xc.numel() / xc.size(-1);
     const int D = (int)xc.size(-1);
-    const bf16* wp = nullptr;
     at::Tensor wc;
     if (w.has_value()) {
         wc = w->contiguous();
         TORCH_CHECK(wc.scalar_type() == xc.scalar_type(), "weight dtype mismatch");
     }
-    if (xc.scalar_type() == at::kBFloat16 && (D % 128) == 0 && D <= 512) {
-        hipLaunchKernelGGL(rms_norm_bf16_row_kernel,
-                           dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
-                           cur_stream(), (const bf16*)xc.data_ptr(),
-                           w.has_value() ? (const bf16*)wc.data_ptr() : nullptr,
-                           (bf16*)out.data_ptr(), rows, D, (float)eps);
-    } else if (xc.scalar_type() == at::kBFloat16 && (D % 8) == 0) {
-        hipLaunchKernelGGL(rms_norm_bf16_kernel, dim3((unsigned)rows), dim3(256), 0,
-                           cur_stream(),
-                           (const bf16*)xc.data_ptr(),
-                           w.has_value() ? (const bf16*)wc.data_ptr() : nullptr,
-                           (bf16*)out.data_ptr(), D, (float)eps);
-    } else if (xc.scalar_type() == at::kFloat) {
+    const auto st = xc.scalar_type();
+    const void* wptr = w.has_value() ? wc.data_ptr() : nullptr;
+    if (is_elem16(st) && (D % 128) == 0 && D <= 512) {
+        PA_WITH_ELEM16(st, hipLaunchKernelGGL(
+            rms_norm_row_kernel<E>, dim3((unsigned)((rows + 3) / 4)),
+            dim3(256), 0, cur_stream(), (const E*)xc.data_ptr(),
+            (const E*)wptr, (E*)out.data_ptr(), rows, D, (float)eps));
+    } else if (is_elem16(st) && (D % 8) == 0) {
+        PA_WITH_ELEM16(st, hipLaunchKernelGGL(
+            rms_norm_vec_kernel<E>, dim3((unsigned)rows), dim3(256), 0,
+            cur_stream(), (const E*)xc.data_ptr(), (const E*)wptr,
+            (E*)out.data_ptr(), D, (float)eps));
+    } else if (st == at::kFloat) {
         hipLaunchKernelGGL(rms_norm_kernel<float>, dim3((unsigned)rows), dim3(256), 0,
                            cur_stream(), xc.data_ptr<float>(),
                            w.has_value() ? wc.data_ptr<float>() : nullptr,
                            out.data_ptr<float>(), D, (float)eps);
-    } else if (xc.scalar_type() == at::kBFloat16) {
-        hipLaunchKernelGGL(rms_norm_kernel<bf16>, dim3((unsigned)rows), dim3(256), 0,
-                           cur_stream(), (const bf16*)xc.data_ptr(),
-                           w.has_value() ? (const bf16*)wc.data_ptr() : nullptr,
-                           (bf16*)out.data_ptr(), D, (float)eps);
+    } else if (is_elem16(st)) {
+        PA_WITH_ELEM16(st, hipLaunchKernelGGL(
+            rms_norm_kernel<E>, dim3((unsigned)rows), dim3(256), 0,
+            cur_stream(), (const E*)xc.data_ptr(), (const E*)wptr,
+            (E*)out.data_ptr(), D, (float)eps));
     } else {
-        TORCH_CHECK(false, "rms_norm: unsupported dtype");
+        TORCH_CHECK(false, "rms_norm: unsupported dtype ", st,
+                    " (bf16, fp16 or fp32)");
     }
     return out;
 }
@@ -1129,23 +1212,27 @@ at::Tensor layer_norm_mod(at::Tensor x, at::Tensor scale, at::Tensor shift,
     auto out = at::empty_like(xc);
     const int B = (int)xc.size(0), S = (int)xc.size(1), D = (int)xc.size(2);
     dim3 grid((unsigned)((long)B * S));
-    if (xc.scalar_type() == at::kBFloat16 && (D % 8) == 0) {
-        hipLaunchKernelGGL(layer_norm_mod_bf16_kernel, grid, dim3(256), 0,
-                           cur_stream(), (const bf16*)xc.data_ptr(),
-                           (const bf16*)sc.data_ptr(), (const bf16*)sh.data_ptr(),
-                           (bf16*)out.data_ptr(), S, D, (float)eps);
-    } else if (xc.scalar_type() == at::kBFloat16) {
-        hipLaunchKernelGGL(layer_norm_mod_kernel<bf16>, grid, dim3(256), 0,
-                           cur_stream(), (const bf16*)xc.data_ptr(),
-                           (const bf16*)sc.data_ptr(), (const bf16*)sh.data_ptr(),
-                           (bf16*)out.data_ptr(), S, D, (float)eps);
-    } else if (xc.scalar_type() == at::kFloat) {
+    const auto st = xc.scalar_type();
+    CHECK_SAME_DTYPE(scale, x);
+    CHECK_SAME_DTYPE(shift, x);
+    if (is_elem16(st) && (D % 8) == 0) {
+        PA_WITH_ELEM16(st, hipLaunchKernelGGL(
+            layer_norm_mod_vec_kernel<E>, grid, dim3(256), 0, cur_stream(),
+            (const E*)xc.data_ptr(), (const E*)sc.data_ptr(),
+            (const E*)sh.data_ptr(), (E*)out.data_ptr(), S, D, (float)eps));
+    } else if (is_elem16(st)) {
+        PA_WITH_ELEM16(st, hipLaunchKernelGGL(
+            layer_norm_mod_kernel<E>, grid, dim3(256), 0, cur_stream(),
+            (const E*)xc.data_ptr(), (const E*)sc.data_ptr(),
+            (const E*)sh.data_ptr(), (E*)out.data_ptr(), S, D, (float)eps));
+    } else if (st == at::kFloat) {
         hipLaunchKernelGGL(layer_norm_mod_kernel<float>, grid, dim3(256), 0,
                            cur_stream(), xc.data_ptr<float>(),
                            sc.data_ptr<float>(), sh.data_ptr<float>(),
                            out.data_ptr<float>(), S, D, (float)eps);
     } else {
-        TORCH_CHECK(false, "layer_norm_mod: unsupported dtype");
+        TORCH_CHECK(false, "layer_norm_mod: unsupported dtype ", st,
+                    " (bf16, fp16 or fp32)");
     }
     return out;
 }
@@ -1189,22 +1276,26 @@ at::Tensor gate_residual(at::Tensor res, at::Tensor gate, at::Tensor x) {
     const long total = xc.numel();
     const int S = (int)xc.size(1), D = (int)xc.size(2);
     const int blocks = (int)std::min<long>((total + 255) / 256, 4096);
-    if (xc.scalar_type() == at::kBFloat16 && (D % 8) == 0) {
-        hipLaunchKernelGGL(gate_residual_bf16_kernel, dim3(blocks), dim3(256), 0,
-                           cur_stream(), (const bf16*)rc.data_ptr(),
-                           (const bf16*)gc.data_ptr(), (const bf16*)xc.data_ptr(),
-                           (bf16*)out.data_ptr(), total / 8, S, D / 8);
-    } else if (xc.scalar_type() == at::kBFloat16) {
-        hipLaunchKernelGGL(gate_residual_kernel<bf16>, dim3(blocks), dim3(256), 0,
-                           cur_stream(), (const bf16*)rc.data_ptr(),
-                           (const bf16*)gc.data_ptr(), (const bf16*)xc.data_ptr(),
-                           (bf16*)out.data_ptr(), total, S, D);
-    } else if (xc.scalar_type() == at::kFloat) {
+    const auto st = xc.scalar_type();
+    CHECK_SAME_DTYPE(res, x);
+    CHECK_SAME_DTYPE(gate, x);
+    if (is_elem16(st) && (D % 8) == 0) {
+        PA_WITH_ELEM16(st, hipLaunchKernelGGL(
+            gate_residual_vec_kernel<E>, dim3(blocks), dim3(256), 0,
+            cur_stream(), (const E*)rc.data_ptr(), (const E*)gc.data_ptr(),
+            (const E*)xc.data_ptr(), (E*)out.data_ptr(), total / 8, S, D / 8));
+    } else if (is_elem16(st)) {
+        PA_WITH_ELEM16(st, hipLaunchKernelGGL(
+            gate_residual_kernel<E>, dim3(blocks), dim3(256), 0,
+            cur_stream(), (const E*)rc.data_ptr(), (const E*)gc.data_ptr(),
+            (const E*)xc.data_ptr(), (E*)out.data_ptr(), total, S, D));
+    } else if (st == at::kFloat) {
         hipLaunchKernelGGL(gate_residual_kernel<float>, dim3(blocks), dim3(256), 0,
                            cur_stream(), rc.data_ptr<float>(), gc.data_ptr<float>(),
                            xc.data_ptr<float>(), out.data_ptr<float>(), total, S, D);
     } else {
-        TORCH_CHECK(false, "gate_residual: unsupported dtype");
+        TORCH_CHECK(false, "gate_residual: unsupported dtype ", st,
+                    " (bf16, fp16 or fp32)");
     }
     return out;
 }
@@ -1229,16 +1320,18 @@ at::Tensor group_norm_silu(at::Tensor x, long groups,
         bp = bf.data_ptr<float>();
     }
     dim3 grid((unsigned)(B * groups));
-    if (xc.scalar_type() == at::kBFloat16) {
-        hipLaunchKernelGGL(group_norm_silu_kernel<bf16>, grid, dim3(256), 0,
-                           cur_stream(), (const bf16*)xc.data_ptr(), wp, bp,
-                           (bf16*)out.data_ptr(), C, HW, (int)groups, (float)eps);
+    if (is_elem16(xc.scalar_type())) {
+        PA_WITH_ELEM16(xc.scalar_type(), hipLaunchKernelGGL(
+            group_norm_silu_kernel<E>, grid, dim3(256), 0, cur_stream(),
+            (const E*)xc.data_ptr(), wp, bp, (E*)out.data_ptr(), C, HW,
+            (int)groups, (float)eps));
     } else if (xc.scalar_type() == at::kFloat) {
         hipLaunchKernelGGL(group_norm_silu_kernel<float>, grid, dim3(256), 0,
                            cur_stream(), xc.data_ptr<float>(), wp, bp,
                            out.data_ptr<float>(), C, HW, (int)groups, (float)eps);
     } else {
-        TORCH_CHECK(false, "group_norm_silu: unsupported dtype");
+        TORCH_CHECK(false, "group_norm_silu: unsupported dtype ",
+                    xc.scalar_type(), " (bf16, fp16 or fp32)");
     }
     return out;
 }
@@ -1254,18 +1347,19 @@ at::Tensor rope_apply(at::Tensor x, at::Tensor cs) {
     TORCH_CHECK((int)cc.size(0) == S && (int)cc.size(1) == D / 2, "cs shape");
     const long pairs = xc.numel() / 2;
     const int blocks = (int)std::min<long>((pairs + 255) / 256, 4096);
-    if (xc.scalar_type() == at::kBFloat16) {
-        hipLaunchKernelGGL(rope_apply_kernel<bf16>, dim3(blocks), dim3(256), 0,
-                           cur_stream(), (const bf16*)xc.data_ptr(),
-                           cc.data_ptr<float>(), (bf16*)out.data_ptr(),
-                           pairs, S, D / 2);
+    if (is_elem16(xc.scalar_type())) {
+        PA_WITH_ELEM16(xc.scalar_type(), hipLaunchKernelGGL(
+            rope_apply_kernel<E>, dim3(blocks), dim3(256), 0, cur_stream(),
+            (const E*)xc.data_ptr(), cc.data_ptr<float>(),
+            (E*)out.data_ptr(), pairs, S, D / 2));
     } else if (xc.scalar_type() == at::kFloat) {
         hipLaunchKernelGGL(rope_apply_kernel<float>, dim3(blocks), dim3(256), 0,
                            cur_stream(), xc.data_ptr<float>(),
                            cc.data_ptr<float>(), out.data_ptr<float>(),
                            pairs, S, D / 2);
     } else {
-        TORCH_CHECK(false, "rope_apply: unsupported dtype");
+        TORCH_CHECK(false, "rope_apply: unsupported dtype ",
+                    xc.scalar_type(), " (bf16, fp16 or fp32)");
     }
     return out;
 }
@@ -1320,7 +1414,11 @@ void qk_norm_rope_(at::Tensor q, at::Tensor k, at::Tensor wq, at::Tensor wk,
                    at::Tensor cs, double eps) {
     CHECK_GPU(q);
     TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "qk_norm_rope_: [B,S,H,D] views");
-    TORCH_CHECK(q.scalar_type() == at::kBFloat16, "qk_norm_rope_: bf16 only");
+    TORCH_CHECK(is_elem16(q.scalar_type()),
+                "qk_norm_rope_: bf16 or fp16 only, got ", q.scalar_type());
+    CHECK_SAME_DTYPE(k, q);
+    CHECK_SAME_DTYPE(wq, q);
+    CHECK_SAME_DTYPE(wk, q);
     TORCH_CHECK(q.stride(3) == 1 && k.stride(3) == 1, "last dim contiguous");
     const int B = (int)q.size(0), S = (int)q.size(1), H = (int)q.size(2),
               D = (int)q.size(3);
@@ -1332,12 +1430,13 @@ void qk_norm_rope_(at::Tensor q, at::Tensor k, at::Tensor wq, at::Tensor wk,
     auto wkc = wk.contiguous();
     const long rows = (long)B * S * H;
     const long blocks = (((rows + 3) / 4) * 64 + 255) / 256;
-    hipLaunchKernelGGL(qk_norm_rope_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                       cur_stream(), (bf16*)q.data_ptr(), (bf16*)k.data_ptr(),
-                       (const bf16*)wqc.data_ptr(), (const bf16*)wkc.data_ptr(),
-                       csf.data_ptr<float>(), S, H, D,
-                       q.stride(0), q.stride(2), q.stride(1),
-                       k.stride(0), k.stride(2), k.stride(1), rows, (float)eps);
+    PA_WITH_ELEM16(q.scalar_type(), hipLaunchKernelGGL(
+        qk_norm_rope_kernel<E>, dim3((unsigned)blocks), dim3(256), 0,
+        cur_stream(), (E*)q.data_ptr(), (E*)k.data_ptr(),
+        (const E*)wqc.data_ptr(), (const E*)wkc.data_ptr(),
+        csf.data_ptr<float>(), S, H, D,
+        q.stride(0), q.stride(2), q.stride(1),
+        k.stride(0), k.stride(2), k.stride(1), rows, (float)eps));
 }
 
 
@@ -1349,18 +1448,20 @@ void qk_norm_rope_(at::Tensor q, at::Tensor k, at::Tensor wq, at::Tensor wk,
 // replacing three strided torch.cat copies plus two qk_norm_rope passes
 // with a single bandwidth pass. One wave per (b, s, h); lane = pair index.
 // ---------------------------------------------------------------------------
+template <typename E>
 __global__ void pack_joint_qkv_kernel(
-    const bf16* __restrict__ txt, const bf16* __restrict__ img,
-    const bf16* __restrict__ wq_t, const bf16* __restrict__ wk_t,
-    const bf16* __restrict__ wq_i, const bf16* __restrict__ wk_i,
+    const E* __restrict__ txt, const E* __restrict__ img,
+    const E* __restrict__ wq_t, const E* __restrict__ wk_t,
+    const E* __restrict__ wq_i, const E* __restrict__ wk_i,
     const float* __restrict__ cs,                   // [T+Si][D/2][2]
-    bf16* __restrict__ oq, bf16* __restrict__ ok, bf16* __restrict__ ov,
+    E* __restrict__ oq, E* __restrict__ ok, E* __restrict__ ov,
     int T, int Si, int H, int D,
     long t_bs, long t_ss, long t_qs, long t_hs,     // txt strides (b, s, qkv, h)
     long i_bs, long i_ss, long i_qs, long i_hs,
     long n_rows, float eps) {
     // RPW rows per wave, all 3*RPW loads issued before the reductions
     // (single-row version measured latency-bound like qk_norm_rope).
+    using EL = Elem16<E>;
     constexpr int RPW = 4;
     const int lane = threadIdx.x & 63;
     const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -1383,7 +1484,7 @@ __global__ void pack_joint_qkv_kernel(
         const int sj = (int)(sh / H);
         const int h = (int)(sh % H);
         const bool is_txt = sj < T;
-        const bf16* src = is_txt
+        const E* src = is_txt
             ? txt + b * t_bs + (long)sj * t_ss + (long)h * t_hs
             : img + b * i_bs + (long)(sj - T) * i_ss + (long)h * i_hs;
         const long qs = is_txt ? t_qs : i_qs;
@@ -1401,32 +1502,32 @@ __global__ void pack_joint_qkv_kernel(
         if (wave * RPW + i >= n_rows) break;
         const float c = cvec[i], sn = svec[i];
         {   // q: rms + weight + rope
-            float a0 = bf2f(__ushort_as_bfloat16((unsigned short)(uq[i] & 0xffff)));
-            float a1 = bf2f(__ushort_as_bfloat16((unsigned short)(uq[i] >> 16)));
+            float a0 = EL::ld((unsigned short)(uq[i] & 0xffff));
+            float a1 = EL::ld((unsigned short)(uq[i] >> 16));
             float ss_ = act ? a0 * a0 + a1 * a1 : 0.f;
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) ss_ += __shfl_xor(ss_, off, 64);
             const float rr = rsqrtf(ss_ / (float)D + eps);
-            a0 = a0 * rr * bf2f(__ushort_as_bfloat16((unsigned short)(uwq[i] & 0xffff)));
-            a1 = a1 * rr * bf2f(__ushort_as_bfloat16((unsigned short)(uwq[i] >> 16)));
+            a0 = a0 * rr * EL::ld((unsigned short)(uwq[i] & 0xffff));
+            a1 = a1 * rr * EL::ld((unsigned short)(uwq[i] >> 16));
             if (act)
                 reinterpret_cast<unsigned int*>(oq)[obase[i] + lane] =
-                    (unsigned int)__bfloat16_as_ushort(f2bf(a0 * c - a1 * sn)) |
-                    ((unsigned int)__bfloat16_as_ushort(f2bf(a0 * sn + a1 * c)) << 16);
+                    (unsigned int)EL::st(a0 * c - a1 * sn) |
+                    ((unsigned int)EL::st(a0 * sn + a1 * c) << 16);
         }
         {   // k
-            float a0 = bf2f(__ushort_as_bfloat16((unsigned short)(uk[i] & 0xffff)));
-            float a1 = bf2f(__ushort_as_bfloat16((unsigned short)(uk[i] >> 16)));
+            float a0 = EL::ld((unsigned short)(uk[i] & 0xffff));
+            float a1 = EL::ld((unsigned short)(uk[i] >> 16));
             float ss_ = act ? a0 * a0 + a1 * a1 : 0.f;
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) ss_ += __shfl_xor(ss_, off, 64);
             const float rr = rsqrtf(ss_ / (float)D + eps);
-            a0 = a0 * rr * bf2f(__ushort_as_bfloat16((unsigned short)(uwk[i] & 0xffff)));
-            a1 = a1 * rr * bf2f(__ushort_as_bfloat16((unsigned short)(uwk[i] >> 16)));
+            a0 = a0 * rr * EL::ld((unsigned short)(uwk[i] & 0xffff));
+            a1 = a1 * rr * EL::ld((unsigned short)(uwk[i] >> 16));
             if (act)
                 reinterpret_cast<unsigned int*>(ok)[obase[i] + lane] =
-                    (unsigned int)__bfloat16_as_ushort(f2bf(a0 * c - a1 * sn)) |
-                    ((unsigned int)__bfloat16_as_ushort(f2bf(a0 * sn + a1 * c)) << 16);
+                    (unsigned int)EL::st(a0 * c - a1 * sn) |
+                    ((unsigned int)EL::st(a0 * sn + a1 * c) << 16);
         }
         if (act) reinterpret_cast<unsigned int*>(ov)[obase[i] + lane] = uv[i];
     }
@@ -1460,34 +1561,27 @@ __global__ void pack_joint_qkv_kernel(
 // LDS = K[64][D+8] + row-major V[64][160] = 37.9 KB (D=128) -> two blocks
 // co-resident per CU, NOT barrier-synced against each other.
 // ---------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-PA_DEV f32x16 mfma32x32x16(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-PA_DEV unsigned int cvt_pk_bf16(float lo, float hi) {
-    unsigned int r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-
-template <int D>
+// The element type E (bf16 or _Float16) enters at three points only: the
+// MFMA opcode, the P pack (Elem16<E>::pack2) and the epilogue cast. Every
+// LDS layout, tr read and permlane swap is a 16-bit move and is shared;
+// the mask sentinel, online-softmax state and accumulators stay fp32.
+template <int D, typename E>
 __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
-    const bf16* __restrict__ q, const bf16* __restrict__ k,
-    const bf16* __restrict__ v, bf16* __restrict__ out,
+    const E* __restrict__ q, const E* __restrict__ k,
+    const E* __restrict__ v, E* __restrict__ out,
     int S, int Sk, float scale, int H,
     long q_bs, long q_hs, int q_ss,
     long k_bs, long k_hs, int k_ss,
     long v_bs, long v_hs, int v_ss,
     long o_bs, long o_hs, int o_ss, int xcd_grid,
-    bf16* __restrict__ out2, int s_split,
+    E* __restrict__ out2, int s_split,
     long o2_bs, long o2_hs, int o2_ss) {
+    using EL = Elem16<E>;
     constexpr int KVBLK = 64;
     constexpr int WAVES = 8;
     constexpr int THREADS = WAVES * 64;
     constexpr int KPAD = D + 8;
-    constexpr int VROW = 160;         // V row stride: 40 granules ≡ 8 mod 32
+    constexpr int VROW = 160;        // V row stride: 40 granules ≡ 8 mod 32
     constexpr int KK = D / 16;        // QK^T K-steps per 32-key tile
     constexpr int NV = D / 32;        // PV dim tiles
     constexpr int KVECS = (KVBLK * D) / (8 * THREADS);
@@ -1495,8 +1589,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     // 1-barrier pipelined schedule; D=64 keeps the v4 2-barrier loop.
     constexpr int DBUF = (D == 128) ? 2 : 1;
 
-    __shared__ bf16 k_lds[DBUF * KVBLK * KPAD];
-    __shared__ bf16 v_lds[DBUF * KVBLK * VROW];
+    __shared__ E k_lds[DBUF * KVBLK * KPAD];
+    __shared__ E v_lds[DBUF * KVBLK * VROW];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1527,11 +1621,11 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     const int h = (int)(bh % H);
     const int q0 = qtile * (WAVES * 32) + wid * 32;
 
-    const bf16* qp = q + b * q_bs + (long)h * q_hs;
-    const bf16* kp = k + b * k_bs + (long)h * k_hs;
-    const bf16* vp = v + b * v_bs + (long)h * v_hs;
-    bf16* op = out + b * o_bs + (long)h * o_hs;
-    bf16* op2 = out2 ? out2 + b * o2_bs + (long)h * o2_hs : nullptr;
+    const E* qp = q + b * q_bs + (long)h * q_hs;
+    const E* kp = k + b * k_bs + (long)h * k_hs;
+    const E* vp = v + b * v_bs + (long)h * v_hs;
+    E* op = out + b * o_bs + (long)h * o_hs;
+    E* op2 = out2 ? out2 + b * o2_bs + (long)h * o2_hs : nullptr;
 
     // Q fragments (B-operand of the swapped QK^T): lane holds
     // Q[q0 + l32][kk*16 + hi*8 + j], j = 0..7.
@@ -1608,7 +1702,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
                 bf16x8 afrag = *reinterpret_cast<const bf16x8*>(
                     &k_lds[buf * (KVBLK * KPAD) + (kt * 32 + l32) * KPAD +
                            kk * 16 + hi * 8]);
-                st[kt] = mfma32x32x16(afrag, qfrag[kk], st[kt]);
+                st[kt] = EL::mfma32(afrag, qfrag[kk], st[kt]);
             }
         }
         __builtin_amdgcn_s_setprio(0);
@@ -1650,17 +1744,17 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
 #pragma unroll
                 for (int r = 0; r < 16; ++r) o_acc[n][r] *= alpha;
         }
-        // P f32 -> bf16 fragments via cvt_pk + permlane32_swap: chunk c
+        // P f32 -> 16-bit fragments via cvt_pk + permlane32_swap: chunk c
         // (16 keys) uses regs 8*(c&1)..+7 of st[c>>1]; after the half-swap
         // each lane holds P[row l32][chunk base + hi*8 + j].
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const f32x16& sv = st[c >> 1];
             const int rb = 8 * (c & 1);
-            unsigned int w0 = cvt_pk_bf16(sv[rb + 0], sv[rb + 1]);
-            unsigned int w1 = cvt_pk_bf16(sv[rb + 2], sv[rb + 3]);
-            unsigned int w2 = cvt_pk_bf16(sv[rb + 4], sv[rb + 5]);
-            unsigned int w3 = cvt_pk_bf16(sv[rb + 6], sv[rb + 7]);
+            unsigned int w0 = EL::pack2(sv[rb + 0], sv[rb + 1]);
+            unsigned int w1 = EL::pack2(sv[rb + 2], sv[rb + 3]);
+            unsigned int w2 = EL::pack2(sv[rb + 4], sv[rb + 5]);
+            unsigned int w3 = EL::pack2(sv[rb + 6], sv[rb + 7]);
             auto r02 = __builtin_amdgcn_permlane32_swap(w0, w2, false, false);
             auto r13 = __builtin_amdgcn_permlane32_swap(w1, w3, false, false);
             unsigned int d[4] = {(unsigned int)r02[0], (unsigned int)r13[0],
@@ -1686,7 +1780,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
                                4 * VROW + n * 32]);
                 bf16x8 va = __builtin_shufflevector(alo, ahi,
                                                     0, 1, 2, 3, 4, 5, 6, 7);
-                o_acc[n] = mfma32x32x16(va, pfrag[c], o_acc[n]);
+                o_acc[n] = EL::mfma32(va, pfrag[c], o_acc[n]);
             }
         }
         __builtin_amdgcn_s_setprio(0);
@@ -1740,7 +1834,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
         // split-stream output: rows >= s_split land in out2 (per-stream
         // contiguous buffers feed the txt/img projections with no reshape
         // copies)
-        bf16* obase;
+        E* obase;
         long orow;
         int oss;
         if (op2 != nullptr && row >= s_split) {
@@ -1762,8 +1856,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
                 unsigned short pack[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    pack[j] = __bfloat16_as_ushort(
-                        f2bf(o_acc[n][r2 * 4 + j] * inv_l));
+                    pack[j] = EL::st(o_acc[n][r2 * 4 + j] * inv_l);
                 *reinterpret_cast<unsigned long long*>(
                     obase + orow * oss + dim0) =
                     *reinterpret_cast<unsigned long long*>(pack);
@@ -1812,26 +1905,26 @@ at::Tensor gelu_tanh(at::Tensor x) {
             if (x.stride(d) != expect) { rowable = false; break; }
         }
     }
-    if (x.scalar_type() == at::kBFloat16 && rowable && (w % 8) == 0 &&
+    if (is_elem16(x.scalar_type()) && rowable && (w % 8) == 0 &&
         (in_stride % 8) == 0) {
         auto out = at::empty(x.sizes(), x.options());
         const long total8 = rows * (w / 8);
         const int blocks = (int)std::min<long>((total8 + 255) / 256, 4096);
-        hipLaunchKernelGGL(gelu_tanh_bf16_kernel, dim3(blocks), dim3(256), 0,
-                           cur_stream(), (const bf16*)x.data_ptr(),
-                           (bf16*)out.data_ptr(), total8, rows, w / 8,
-                           in_stride / 8);
+        PA_WITH_ELEM16(x.scalar_type(), hipLaunchKernelGGL(
+            gelu_tanh_vec_kernel<E>, dim3(blocks), dim3(256), 0,
+            cur_stream(), (const E*)x.data_ptr(), (E*)out.data_ptr(),
+            total8, rows, w / 8, in_stride / 8));
         return out;
     }
     auto xc = x.contiguous();
     auto out = at::empty_like(xc);
-    if (xc.scalar_type() == at::kBFloat16 && (xc.numel() % 8) == 0) {
+    if (is_elem16(xc.scalar_type()) && (xc.numel() % 8) == 0) {
         const long total8 = xc.numel() / 8;
         const int blocks = (int)std::min<long>((total8 + 255) / 256, 4096);
-        hipLaunchKernelGGL(gelu_tanh_bf16_kernel, dim3(blocks), dim3(256), 0,
-                           cur_stream(), (const bf16*)xc.data_ptr(),
-                           (bf16*)out.data_ptr(), total8, xc.numel() / 8,
-                           xc.numel() / 8, xc.numel() / 8);
+        PA_WITH_ELEM16(xc.scalar_type(), hipLaunchKernelGGL(
+            gelu_tanh_vec_kernel<E>, dim3(blocks), dim3(256), 0,
+            cur_stream(), (const E*)xc.data_ptr(), (E*)out.data_ptr(),
+            total8, xc.numel() / 8, xc.numel() / 8, xc.numel() / 8));
         return out;
     }
     return at::gelu(xc, "tanh");
@@ -1845,7 +1938,14 @@ std::vector<at::Tensor> pack_joint_qkv(at::Tensor txt_qkv, at::Tensor img_qkv,
     CHECK_GPU(txt_qkv);
     TORCH_CHECK(txt_qkv.dim() == 5 && img_qkv.dim() == 5,
                 "pack_joint_qkv expects [B,S,3,H,D] views");
-    TORCH_CHECK(txt_qkv.scalar_type() == at::kBFloat16, "bf16 only");
+    TORCH_CHECK(is_elem16(txt_qkv.scalar_type()),
+                "pack_joint_qkv: bf16 or fp16 only, got ",
+                txt_qkv.scalar_type());
+    CHECK_SAME_DTYPE(img_qkv, txt_qkv);
+    CHECK_SAME_DTYPE(wq_t, txt_qkv);
+    CHECK_SAME_DTYPE(wk_t, txt_qkv);
+    CHECK_SAME_DTYPE(wq_i, txt_qkv);
+    CHECK_SAME_DTYPE(wk_i, txt_qkv);
     const int B = (int)txt_qkv.size(0), T = (int)txt_qkv.size(1),
               H = (int)txt_qkv.size(3), D = (int)txt_qkv.size(4);
     const int Si = (int)img_qkv.size(1);
@@ -1860,22 +1960,22 @@ std::vector<at::Tensor> pack_joint_qkv(at::Tensor txt_qkv, at::Tensor img_qkv,
     auto ov = at::empty({B, T + Si, H, D}, opts);
     const long rows = (long)B * (T + Si) * H;
     const long blocks = (((rows + 3) / 4) * 64 + 255) / 256;
-    hipLaunchKernelGGL(pack_joint_qkv_kernel, dim3((unsigned)blocks), dim3(256),
-                       0, cur_stream(),
-                       (const bf16*)txt_qkv.data_ptr(),
-                       (const bf16*)img_qkv.data_ptr(),
-                       (const bf16*)wq_t.contiguous().data_ptr(),
-                       (const bf16*)wk_t.contiguous().data_ptr(),
-                       (const bf16*)wq_i.contiguous().data_ptr(),
-                       (const bf16*)wk_i.contiguous().data_ptr(),
-                       csf.data_ptr<float>(),
-                       (bf16*)oq.data_ptr(), (bf16*)ok.data_ptr(),
-                       (bf16*)ov.data_ptr(), T, Si, H, D,
-                       txt_qkv.stride(0), txt_qkv.stride(1), txt_qkv.stride(2),
-                       txt_qkv.stride(3),
-                       img_qkv.stride(0), img_qkv.stride(1), img_qkv.stride(2),
-                       img_qkv.stride(3),
-                       rows, (float)eps);
+    auto wqtc = wq_t.contiguous(), wktc = wk_t.contiguous();
+    auto wqic = wq_i.contiguous(), wkic = wk_i.contiguous();
+    PA_WITH_ELEM16(txt_qkv.scalar_type(), hipLaunchKernelGGL(
+        pack_joint_qkv_kernel<E>, dim3((unsigned)blocks), dim3(256),
+        0, cur_stream(),
+        (const E*)txt_qkv.data_ptr(), (const E*)img_qkv.data_ptr(),
+        (const E*)wqtc.data_ptr(), (const E*)wktc.data_ptr(),
+        (const E*)wqic.data_ptr(), (const E*)wkic.data_ptr(),
+        csf.data_ptr<float>(),
+        (E*)oq.data_ptr(), (E*)ok.data_ptr(), (E*)ov.data_ptr(),
+        T, Si, H, D,
+        txt_qkv.stride(0), txt_qkv.stride(1), txt_qkv.stride(2),
+        txt_qkv.stride(3),
+        img_qkv.stride(0), img_qkv.stride(1), img_qkv.stride(2),
+        img_qkv.stride(3),
+        rows, (float)eps));
     return {oq, ok, ov};
 }
 
@@ -1931,7 +2031,10 @@ static std::vector<at::Tensor> attn_fwd_launch_split(
     at::Tensor q, at::Tensor k, at::Tensor v, double scale, bool bshd,
     long split) {
     CHECK_GPU(q);
-    TORCH_CHECK(q.scalar_type() == at::kBFloat16, "attn_fwd: bf16 only");
+    TORCH_CHECK(is_elem16(q.scalar_type()),
+                "attn_fwd: bf16 or fp16 only, got ", q.scalar_type());
+    CHECK_SAME_DTYPE(k, q);
+    CHECK_SAME_DTYPE(v, q);
     TORCH_CHECK(q.dim() == 4, "attn_fwd expects 4-D q/k/v");
     // layouts: bshd = [B, S, H, D] (strided views allowed),
     //          else  = [B, H, S, D] (must be row-contiguous per head)
@@ -1956,12 +2059,12 @@ static std::vector<at::Tensor> attn_fwd_launch_split(
         ? at::empty({B, do_split ? (int)split : S, H, D}, qc.options())
         : at::empty({B, H, S, D}, qc.options());
     at::Tensor out2;
-    bf16* o2p = nullptr;
+    void* o2p = nullptr;
     long o2_bs = 0, o2_hs = 0, ssplit = S;
     int o2_ss = 0;
     if (do_split) {
         out2 = at::empty({B, S - (int)split, H, D}, qc.options());
-        o2p = (bf16*)out2.data_ptr();
+        o2p = out2.data_ptr();
         o2_bs = out2.stride(0);
         o2_hs = out2.stride(2);
         o2_ss = (int)out2.stride(1);
@@ -1974,13 +2077,19 @@ static std::vector<at::Tensor> attn_fwd_launch_split(
     int xcd_grid = 0;
     dim3 grid_v4((unsigned)((S + 255) / 256), (unsigned)((long)B * H));
     dim3 grid((unsigned)((S + 255) / 256), (unsigned)((long)B * H));
-#define PA_ATTN_ARGS                                                          \
-    (const bf16*)qc.data_ptr(), (const bf16*)kc.data_ptr(),                   \
-    (const bf16*)vc.data_ptr(), (bf16*)out.data_ptr(), S, Sk, (float)scale, H, \
+#define PA_ATTN_ARGS_T(T)                                                     \
+    (const T*)qc.data_ptr(), (const T*)kc.data_ptr(),                         \
+    (const T*)vc.data_ptr(), (T*)out.data_ptr(), S, Sk, (float)scale, H,      \
     qc.stride(b_ax), qc.stride(h_ax), (int)qc.stride(s_ax),                   \
     kc.stride(b_ax), kc.stride(h_ax), (int)kc.stride(s_ax),                   \
     vc.stride(b_ax), vc.stride(h_ax), (int)vc.stride(s_ax),                   \
     out.stride(b_ax), out.stride(h_ax), (int)out.stride(s_ax)
+#define PA_ATTN_ARGS PA_ATTN_ARGS_T(bf16)
+    // the previous-generation debug kernel has no fp16 instantiation; its
+    // bf16 conversions must never see fp16 bits
+    TORCH_CHECK(!use_v3 || qc.scalar_type() == at::kBFloat16,
+                "attn_fwd: PA_ATTN_V3=1 selects the bf16-only debug kernel; "
+                "got ", qc.scalar_type(), " — unset PA_ATTN_V3 for fp16");
     if (!use_v3) {
         const long BH = (long)B * H;
         const unsigned nq = (unsigned)((S + 255) / 256);
@@ -1990,13 +2099,15 @@ static std::vector<at::Tensor> attn_fwd_launch_split(
             xcd_grid = 1;
         }
         if (D == 128) {
-            hipLaunchKernelGGL(attn_fwd_v4_kernel<128>, grid_v4, dim3(512), 0,
-                               cur_stream(), PA_ATTN_ARGS, xcd_grid,
-                               o2p, ssplit, o2_bs, o2_hs, o2_ss);
+            PA_WITH_ELEM16(qc.scalar_type(), hipLaunchKernelGGL(
+                HIP_KERNEL_NAME(attn_fwd_v4_kernel<128, E>), grid_v4,
+                dim3(512), 0, cur_stream(), PA_ATTN_ARGS_T(E), xcd_grid,
+                (E*)o2p, ssplit, o2_bs, o2_hs, o2_ss));
         } else {
-            hipLaunchKernelGGL(attn_fwd_v4_kernel<64>, grid_v4, dim3(512), 0,
-                               cur_stream(), PA_ATTN_ARGS, xcd_grid,
-                               o2p, ssplit, o2_bs, o2_hs, o2_ss);
+            PA_WITH_ELEM16(qc.scalar_type(), hipLaunchKernelGGL(
+                HIP_KERNEL_NAME(attn_fwd_v4_kernel<64, E>), grid_v4,
+                dim3(512), 0, cur_stream(), PA_ATTN_ARGS_T(E), xcd_grid,
+                (E*)o2p, ssplit, o2_bs, o2_hs, o2_ss));
         }
     } else if (D == 128) {
         TORCH_CHECK(!do_split, "split output needs the v4 kernel");
@@ -2007,6 +2118,7 @@ static std::vector<at::Tensor> attn_fwd_launch_split(
                            cur_stream(), PA_ATTN_ARGS);
     }
 #undef PA_ATTN_ARGS
+#undef PA_ATTN_ARGS_T
     if (do_split) return {out, out2};
     return {out};
 }
@@ -2037,7 +2149,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("bias") = py::none(), py::arg("eps") = 1e-6);
     m.def("rope_apply", &rope_apply, "RoPE apply (gfx950)");
     m.def("timestep_embedding", &timestep_embedding, "Sinusoidal timestep embedding");
-    m.def("attn_fwd", &attn_fwd, "Fused flash attention fwd, bf16 MFMA (gfx950)");
+    m.def("attn_fwd", &attn_fwd,
+          "Fused flash attention fwd, bf16/fp16 MFMA (gfx950)");
     m.def("attn_fwd_bshd", &attn_fwd_bshd,
           "Fused flash attention fwd on [B,S,H,D] strided views (gfx950)");
     m.def("attn_fwd_bshd_split", &attn_fwd_bshd_split,

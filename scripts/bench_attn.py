@@ -3,7 +3,12 @@
 
 Reports TF/s for the fused attention kernel at FLUX/SDXL/WAN shapes and
 times the per-layer fused ops; also a hipBLASLt bf16 GEMM reference to show
-the roofline context. Random data (guide §5.4 rule 25)."""
+the roofline context. Random data (guide §5.4 rule 25).
+
+--dtype {bf16,fp16} picks the element type of the attention and fused-op
+sections (default bf16); the hipBLASLt reference stays bf16. --attn-only
+stops after the attention section (for dtype A/B runs)."""
+import argparse
 import sys
 import time
 
@@ -29,21 +34,28 @@ def attn_flops(B, H, S, D):
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16")
+    ap.add_argument("--attn-only", action="store_true")
+    args = ap.parse_args()
+    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
     assert torch.cuda.is_available()
     dev = "cuda"
-    print("== attention (bf16, random data) ==")
+    print(f"== attention ({args.dtype}, random data) ==")
     for name, (B, H, S, D) in {
         "flux_b8": (8, 24, 4608, 128),
         "flux_b1": (1, 24, 4608, 128),
         "sdxl_mid": (4, 20, 1024, 64),
         "square_2k": (16, 16, 2048, 128),
     }.items():
-        q = torch.randn(B, H, S, D, device=dev, dtype=torch.bfloat16)
+        q = torch.randn(B, H, S, D, device=dev, dtype=dtype)
         k = torch.randn_like(q)
         v = torch.randn_like(q)
         dt = timeit(lambda: ops.attention(q, k, v), iters=10)
         tf = attn_flops(B, H, S, D) / dt / 1e12
         print(f"  {name:10s} B{B} H{H} S{S} D{D}: {dt*1e3:8.2f} ms  {tf:7.1f} TF/s")
+    if args.attn_only:
+        return
 
     print("== hipBLASLt bf16 GEMM reference ==")
     for n in (4096, 8192):
@@ -59,18 +71,18 @@ def main():
         dt = timeit(lambda: torch.nn.functional.linear(a, w), iters=10)
         print(f"  linear {m}x{k_}x{n}: {dt*1e3:8.2f} ms  {2*m*k_*n/dt/1e12:7.1f} TF/s")
 
-    print("== fused elementwise ops (FLUX shapes, batch 8) ==")
+    print(f"== fused elementwise ops ({args.dtype}, FLUX shapes, batch 8) ==")
     B, S, Dm = 8, 4608, 3072
-    x = torch.randn(B, S, Dm, device=dev, dtype=torch.bfloat16)
-    sc = torch.randn(B, Dm, device=dev, dtype=torch.bfloat16)
+    x = torch.randn(B, S, Dm, device=dev, dtype=dtype)
+    sc = torch.randn(B, Dm, device=dev, dtype=dtype)
     sh = torch.randn_like(sc)
     dt = timeit(lambda: ops.layer_norm_mod(x, sc, sh))
     gbs = 2 * x.numel() * 2 / dt / 1e9
     print(f"  layer_norm_mod: {dt*1e3:7.3f} ms  {gbs:7.0f} GB/s")
     dt = timeit(lambda: ops.gate_residual(x, sc, x))
     print(f"  gate_residual:  {dt*1e3:7.3f} ms  {3*x.numel()*2/dt/1e9:7.0f} GB/s")
-    qh = torch.randn(B, 24, S, 128, device=dev, dtype=torch.bfloat16)
-    w = torch.randn(128, device=dev, dtype=torch.bfloat16)
+    qh = torch.randn(B, 24, S, 128, device=dev, dtype=dtype)
+    w = torch.randn(128, device=dev, dtype=dtype)
     dt = timeit(lambda: ops.rms_norm(qh, w))
     print(f"  rms_norm qk:    {dt*1e3:7.3f} ms  {2*qh.numel()*2/dt/1e9:7.0f} GB/s")
     from comfyui_parallelanything_amd.ops import reference as R
