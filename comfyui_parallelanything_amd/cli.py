@@ -48,6 +48,10 @@ def main(argv=None):
     ap.add_argument("--lora", default=None, metavar="PATH[:SCALE]",
                     help="merge a LoRA .safetensors into the weights before "
                          "replication (PEFT or kohya key conventions)")
+    ap.add_argument("--text-len", default=None, metavar="N[,N...]",
+                    help="real prompt length(s): one value for the whole "
+                         "batch or one per sample; the rest of the context "
+                         "is padding, passed to the model as attention_mask")
     ap.add_argument("--json-out", default=None,
                     help="write the run summary as one JSON record")
     args = ap.parse_args(argv)
@@ -95,12 +99,16 @@ def main(argv=None):
     configure_pipeline(engine, microbatches=args.microbatches)
     install_parallel_forward(model, engine)
 
+    text_len = None
+    if args.text_len:
+        lens = [int(n) for n in args.text_len.split(",")]
+        text_len = lens[0] if len(lens) == 1 else lens
     if args.model.startswith("wan"):
         x, t, ctx, kw = make_inputs(args.batch, dev=chain.lead, dtype=dtype,
-                                    tiny=tiny)
+                                    tiny=tiny, text_len=text_len)
     else:
         x, t, ctx, kw = make_inputs(args.batch, px=args.px, dev=chain.lead,
-                                    dtype=dtype, tiny=tiny)
+                                    dtype=dtype, tiny=tiny, text_len=text_len)
 
     timer = StepTimer(devices=list(dict.fromkeys(chain.devices)))
     with torch.no_grad():
@@ -120,7 +128,7 @@ def main(argv=None):
         "model": args.model, "batch": args.batch, "px": args.px,
         "devices": devices, "percent": pcts,
         "dtype": str(dtype).replace("torch.", ""), "tiny": tiny,
-        "engine": "in-process",
+        "engine": "in-process", "text_len": text_len,
     }
     print(json.dumps(summary, indent=2))
     if args.json_out:

@@ -228,6 +228,30 @@ def rope_2d_table(
     return torch.cat(tables, dim=1)  # [S, D/2, 2]
 
 
+def joint_key_mask(attention_mask, B: int, txt_len: int, img_len: int):
+    """Pack the joint txt|img key mask once per forward: the text part is
+    ``attention_mask`` ([B, T], nonzero = real token), image keys are all
+    live. None in, None out (the unmasked kernels run)."""
+    if attention_mask is None:
+        return None
+    m = ops.reference.as_bool_key_mask(attention_mask)
+    if m.shape != (B, txt_len):
+        raise ValueError(f"attention_mask {tuple(m.shape)} does not match "
+                         f"the context [B={B}, T={txt_len}]")
+    ones = torch.ones(B, img_len, dtype=torch.bool, device=m.device)
+    return ops.pack_key_mask(torch.cat([m, ones], dim=1))
+
+
+def context_key_mask(attention_mask, context):
+    """Pack ``attention_mask`` ([B, T] over the context tokens) for the
+    cross-attention of models whose keys are the context alone."""
+    m = ops.reference.as_bool_key_mask(attention_mask)
+    if m.shape != tuple(context.shape[:2]):
+        raise ValueError(f"attention_mask {tuple(m.shape)} does not match "
+                         f"the context {tuple(context.shape[:2])}")
+    return ops.pack_key_mask(m)
+
+
 class JointAttention(nn.Module):
     """Attention core shared by MMDiT blocks (scale holder; the heavy
     lifting is ops.attention_bshd on fused-qkv views)."""
@@ -271,7 +295,8 @@ class DoubleStreamBlock(nn.Module):
         )
         return q, k, v
 
-    def forward(self, img, txt, vec, pe, mods=None):
+    def forward(self, img, txt, vec, pe, mods=None, key_mask=None):
+        # key_mask: optional ops.KeyMask over the joint txt|img keys
         if mods is not None:
             (img_m1, img_m2), (txt_m1, txt_m2) = mods
         else:
@@ -297,7 +322,7 @@ class DoubleStreamBlock(nn.Module):
             pe,
         )
         txt_attn, img_attn = ops.attention_bshd_split(
-            q, k, v, T, self.attn.scale
+            q, k, v, T, self.attn.scale, key_mask=key_mask
         )
         txt_attn = txt_attn.flatten(2)
         img_attn = img_attn.flatten(2)
@@ -334,7 +359,8 @@ class SingleStreamBlock(nn.Module):
         self.modulation = Modulation(hidden, double=False)
         self.attn = JointAttention(num_heads, head_dim)
 
-    def forward(self, x, vec, pe, mods=None):
+    def forward(self, x, vec, pe, mods=None, key_mask=None):
+        # key_mask: optional ops.KeyMask over this sequence's keys
         B, S, hidden = x.shape
         if mods is not None:
             (mod,) = mods
@@ -368,7 +394,8 @@ class SingleStreamBlock(nn.Module):
         ops.qk_norm_rope_(
             q, k, self.norm.query_norm.scale, self.norm.key_norm.scale, pe
         )
-        attn = ops.attention_bshd(q, k, v, self.attn.scale).flatten(2)
+        attn = ops.attention_bshd(q, k, v, self.attn.scale,
+                                  key_mask=key_mask).flatten(2)
         if mlp_fp8 is not None:
             out = self.linear2_attn(attn) + self.linear2_mlp.mm_fp8(*mlp_fp8)
         elif x.is_cuda and isinstance(self.linear2_mlp, nn.Linear):

@@ -27,6 +27,7 @@ from .layers import (
     MLPEmbedder,
     ModulationBank,
     SingleStreamBlock,
+    joint_key_mask,
     rope_2d_table,
 )
 
@@ -141,7 +142,8 @@ class Flux(nn.Module):
         return pe
 
     @torch.no_grad()
-    def forward(self, x, timesteps, context=None, y=None, guidance=None, **kwargs):
+    def forward(self, x, timesteps, context=None, y=None, guidance=None,
+                attention_mask=None, **kwargs):
         cfg = self.cfg
         B = x.shape[0]
         img, h, w = self._patchify(x)
@@ -174,18 +176,24 @@ class Flux(nn.Module):
                 bank = False  # quantized mods: per-block path
             self._mod_cache["bank"] = bank
         banked = bank(vec) if bank else None
+        # masked calls only pass the extra argument, so an unmasked forward
+        # calls every block exactly as before
+        mk = {}
+        if attention_mask is not None:
+            mk["key_mask"] = joint_key_mask(attention_mask, B, txt.shape[1],
+                                            img.shape[1])
 
         i = 0
         for block in self.double_blocks:
             img, txt = block(
                 img, txt, vec, pe,
-                mods=(banked[i], banked[i + 1]) if banked else None,
+                mods=(banked[i], banked[i + 1]) if banked else None, **mk,
             )
             i += 2
         xcat = torch.cat([txt, img], dim=1)
         for block in self.single_blocks:
             xcat = block(xcat, vec, pe,
-                         mods=(banked[i][0],) if banked else None)
+                         mods=(banked[i][0],) if banked else None, **mk)
             i += 1
         img = xcat[:, txt.shape[1]:]
         out = self.final_layer(img, vec)
@@ -247,7 +255,8 @@ class ZImage(nn.Module):
         return pe
 
     @torch.no_grad()
-    def forward(self, x, timesteps, context=None, **kwargs):
+    def forward(self, x, timesteps, context=None, attention_mask=None,
+                **kwargs):
         cfg = self.cfg
         B, C, H, W = x.shape
         p = cfg.patch_size
@@ -272,9 +281,13 @@ class ZImage(nn.Module):
                 bank = False
             self._mod_cache["bank"] = bank
         banked = bank(vec) if bank else None
+        mk = {}
+        if attention_mask is not None:
+            mk["key_mask"] = joint_key_mask(attention_mask, B, txt.shape[1],
+                                            img.shape[1])
         for i, block in enumerate(self.layers):
             seq = block(seq, vec, pe,
-                        mods=(banked[i][0],) if banked else None)
+                        mods=(banked[i][0],) if banked else None, **mk)
         out = self.final_layer(seq[:, txt.shape[1]:], vec)
         return (
             out.view(B, h, w, C, p, p)

@@ -19,6 +19,24 @@ def _latent_hw(px: int) -> int:
     return px // 8  # SD-family VAE stride
 
 
+def _with_text_mask(kw: Dict[str, Any], text_len, ctx) -> Dict[str, Any]:
+    """Add ``attention_mask`` ([B, T] bool, True = real token) when the
+    caller gives prompt lengths: one int for the whole batch or a per-sample
+    list. The context stays T tokens long — positions at or beyond a
+    sample's length are padding the models mask out of every attention."""
+    if text_len is None:
+        return kw
+    B, T = ctx.shape[:2]
+    lens = [int(text_len)] * B if isinstance(text_len, int) else \
+        [int(n) for n in text_len]
+    if len(lens) != B:
+        raise ValueError(f"text_len has {len(lens)} entries for batch {B}")
+    if any(n < 0 or n > T for n in lens):
+        raise ValueError(f"text_len entries must lie in [0, {T}], got {lens}")
+    mask = torch.arange(T)[None, :] < torch.tensor(lens)[:, None]
+    return dict(kw, attention_mask=mask.to(ctx.device))
+
+
 def make_flux(dev="cpu", dtype=torch.bfloat16, tiny=False):
     cfg = FluxConfig.tiny() if tiny else FluxConfig.flux1_dev()
     torch.manual_seed(0)
@@ -28,7 +46,7 @@ def make_flux(dev="cpu", dtype=torch.bfloat16, tiny=False):
 
 
 def flux_inputs(batch: int, px: int = 1024, dev="cpu", dtype=torch.bfloat16,
-                tiny=False, seed: int = 1234):
+                tiny=False, seed: int = 1234, text_len=None):
     cfg = FluxConfig.tiny() if tiny else FluxConfig.flux1_dev()
     g = torch.Generator(device="cpu").manual_seed(seed)
     hw = _latent_hw(px) if not tiny else 16
@@ -37,7 +55,7 @@ def flux_inputs(batch: int, px: int = 1024, dev="cpu", dtype=torch.bfloat16,
     txt_len = 512 if not tiny else 8
     ctx = torch.randn(batch, txt_len, cfg.context_dim, generator=g).to(dev, dtype)
     y = torch.randn(batch, cfg.vec_dim, generator=g).to(dev, dtype)
-    return x, t, ctx, {"y": y}
+    return x, t, ctx, _with_text_mask({"y": y}, text_len, ctx)
 
 
 def make_zimage(dev="cpu", dtype=torch.bfloat16, tiny=False):
@@ -49,7 +67,7 @@ def make_zimage(dev="cpu", dtype=torch.bfloat16, tiny=False):
 
 
 def zimage_inputs(batch: int, px: int = 1024, dev="cpu", dtype=torch.bfloat16,
-                  tiny=False, seed: int = 1234):
+                  tiny=False, seed: int = 1234, text_len=None):
     cfg = ZImageConfig.tiny() if tiny else ZImageConfig.z_image_turbo()
     g = torch.Generator(device="cpu").manual_seed(seed)
     hw = _latent_hw(px) if not tiny else 16
@@ -57,7 +75,7 @@ def zimage_inputs(batch: int, px: int = 1024, dev="cpu", dtype=torch.bfloat16,
     t = torch.rand(batch, generator=g).to(dev, torch.float32)
     txt_len = 64 if not tiny else 8
     ctx = torch.randn(batch, txt_len, cfg.context_dim, generator=g).to(dev, dtype)
-    return x, t, ctx, {}
+    return x, t, ctx, _with_text_mask({}, text_len, ctx)
 
 
 def make_sd15(dev="cpu", dtype=torch.float32, tiny=False):
@@ -69,7 +87,7 @@ def make_sd15(dev="cpu", dtype=torch.float32, tiny=False):
 
 
 def sd15_inputs(batch: int, px: int = 256, dev="cpu", dtype=torch.float32,
-                tiny=False, seed: int = 1234):
+                tiny=False, seed: int = 1234, text_len=None):
     cfg = UNetConfig.tiny() if tiny else UNetConfig.sd15()
     g = torch.Generator(device="cpu").manual_seed(seed)
     hw = _latent_hw(px) if not tiny else 16
@@ -77,7 +95,7 @@ def sd15_inputs(batch: int, px: int = 256, dev="cpu", dtype=torch.float32,
     t = torch.rand(batch, generator=g).to(dev, torch.float32)
     txt_len = 77 if not tiny else 8
     ctx = torch.randn(batch, txt_len, cfg.context_dim, generator=g).to(dev, dtype)
-    return x, t, ctx, {}
+    return x, t, ctx, _with_text_mask({}, text_len, ctx)
 
 
 def make_sdxl(dev="cpu", dtype=torch.bfloat16, tiny=False):
@@ -89,7 +107,7 @@ def make_sdxl(dev="cpu", dtype=torch.bfloat16, tiny=False):
 
 
 def sdxl_inputs(batch: int, px: int = 1024, dev="cpu", dtype=torch.bfloat16,
-                tiny=False, seed: int = 1234):
+                tiny=False, seed: int = 1234, text_len=None):
     cfg = UNetConfig.tiny() if tiny else UNetConfig.sdxl()
     g = torch.Generator(device="cpu").manual_seed(seed)
     hw = _latent_hw(px) if not tiny else 16
@@ -99,7 +117,7 @@ def sdxl_inputs(batch: int, px: int = 1024, dev="cpu", dtype=torch.bfloat16,
     kw = {}
     if cfg.adm_in_channels:
         kw["y"] = torch.randn(batch, cfg.adm_in_channels, generator=g).to(dev, dtype)
-    return x, t, ctx, kw
+    return x, t, ctx, _with_text_mask(kw, text_len, ctx)
 
 
 def make_sd3(dev="cpu", dtype=torch.bfloat16, tiny=False):
@@ -111,7 +129,7 @@ def make_sd3(dev="cpu", dtype=torch.bfloat16, tiny=False):
 
 
 def sd3_inputs(batch: int, px: int = 1024, dev="cpu", dtype=torch.bfloat16,
-               tiny=False, seed: int = 1234):
+               tiny=False, seed: int = 1234, text_len=None):
     cfg = FluxConfig.sd35_tiny() if tiny else FluxConfig.sd35_large()
     g = torch.Generator(device="cpu").manual_seed(seed)
     hw = _latent_hw(px) if not tiny else 16
@@ -120,7 +138,7 @@ def sd3_inputs(batch: int, px: int = 1024, dev="cpu", dtype=torch.bfloat16,
     txt_len = 154 if not tiny else 8
     ctx = torch.randn(batch, txt_len, cfg.context_dim, generator=g).to(dev, dtype)
     y = torch.randn(batch, cfg.vec_dim, generator=g).to(dev, dtype)
-    return x, t, ctx, {"y": y}
+    return x, t, ctx, _with_text_mask({"y": y}, text_len, ctx)
 
 
 def make_wan(dev="cpu", dtype=torch.bfloat16, tiny=False):
@@ -132,7 +150,8 @@ def make_wan(dev="cpu", dtype=torch.bfloat16, tiny=False):
 
 
 def wan_inputs(batch: int, frames: int = 21, h: int = 90, w: int = 160,
-               dev="cpu", dtype=torch.bfloat16, tiny=False, seed: int = 1234):
+               dev="cpu", dtype=torch.bfloat16, tiny=False, seed: int = 1234,
+               text_len=None):
     cfg = WanConfig.tiny() if tiny else WanConfig.wan22_a14b()
     g = torch.Generator(device="cpu").manual_seed(seed)
     if tiny:
@@ -141,7 +160,7 @@ def wan_inputs(batch: int, frames: int = 21, h: int = 90, w: int = 160,
     t = torch.rand(batch, generator=g).to(dev, torch.float32)
     txt_len = 512 if not tiny else 8
     ctx = torch.randn(batch, txt_len, cfg.ctx_dim, generator=g).to(dev, dtype)
-    return x, t, ctx, {}
+    return x, t, ctx, _with_text_mask({}, text_len, ctx)
 
 
 def make_wan5b(dev="cpu", dtype=torch.bfloat16, tiny=False):
@@ -154,7 +173,7 @@ def make_wan5b(dev="cpu", dtype=torch.bfloat16, tiny=False):
 
 def wan5b_inputs(batch: int, frames: int = 21, h: int = 90, w: int = 160,
                  dev="cpu", dtype=torch.bfloat16, tiny=False,
-                 seed: int = 1234):
+                 seed: int = 1234, text_len=None):
     cfg = WanConfig.tiny() if tiny else WanConfig.wan22_5b()
     g = torch.Generator(device="cpu").manual_seed(seed)
     if tiny:
@@ -163,7 +182,7 @@ def wan5b_inputs(batch: int, frames: int = 21, h: int = 90, w: int = 160,
     t = torch.rand(batch, generator=g).to(dev, torch.float32)
     txt_len = 512 if not tiny else 8
     ctx = torch.randn(batch, txt_len, cfg.ctx_dim, generator=g).to(dev, dtype)
-    return x, t, ctx, {}
+    return x, t, ctx, _with_text_mask({}, text_len, ctx)
 
 
 def make_wan_i2v(dev="cpu", dtype=torch.bfloat16, tiny=False):
@@ -176,7 +195,7 @@ def make_wan_i2v(dev="cpu", dtype=torch.bfloat16, tiny=False):
 
 def wan_i2v_inputs(batch: int, frames: int = 21, h: int = 90, w: int = 160,
                    dev="cpu", dtype=torch.bfloat16, tiny=False,
-                   seed: int = 1234):
+                   seed: int = 1234, text_len=None):
     """WAN2.2 I2V (BASELINE config 5: 720p batch 4): text-to-video inputs
     plus the channel-concatenated image conditioning — first-frame mask +
     reference-image VAE latent, zero on later frames."""
@@ -194,7 +213,7 @@ def wan_i2v_inputs(batch: int, frames: int = 21, h: int = 90, w: int = 160,
     cond[:, mask_ch:, 0] = torch.randn(
         batch, cfg.in_channels, h, w, generator=g
     )  # reference-image latent on frame 0
-    return x, t, ctx, {"image_cond": cond.to(dev, dtype)}
+    return x, t, ctx, _with_text_mask({"image_cond": cond.to(dev, dtype)}, text_len, ctx)
 
 
 MODELS: Dict[str, Tuple[Callable, Callable]] = {

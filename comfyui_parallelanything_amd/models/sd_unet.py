@@ -18,6 +18,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from .layers import context_key_mask
 
 
 class GNSiLU(nn.Module):
@@ -58,13 +59,14 @@ class CrossAttention(nn.Module):
         self.to_out = nn.Linear(dim, dim)
         self.scale = 1.0 / math.sqrt(dim // num_heads)
 
-    def forward(self, x, context=None):
+    def forward(self, x, context=None, key_mask=None):
         ctx = x if context is None else context
         H = self.num_heads
         q = self.to_q(x).unflatten(-1, (H, -1))
         k = self.to_k(ctx).unflatten(-1, (H, -1))
         v = self.to_v(ctx).unflatten(-1, (H, -1))
-        return self.to_out(ops.attention_bshd(q, k, v, self.scale).flatten(2))
+        return self.to_out(ops.attention_bshd(
+            q, k, v, self.scale, key_mask=key_mask).flatten(2))
 
 
 class GEGLU(nn.Module):
@@ -87,9 +89,10 @@ class TransformerBlock(nn.Module):
         self.norm3 = nn.LayerNorm(dim)
         self.ff = nn.Sequential(GEGLU(dim, dim * 4), nn.Linear(dim * 4, dim))
 
-    def forward(self, x, context=None):
+    def forward(self, x, context=None, key_mask=None):
+        # key_mask covers the context tokens: cross-attention (attn2) only
         x = x + self.attn1(self.norm1(x))
-        x = x + self.attn2(self.norm2(x), context)
+        x = x + self.attn2(self.norm2(x), context, key_mask)
         x = x + self.ff(self.norm3(x))
         return x
 
@@ -104,12 +107,12 @@ class SpatialTransformer(nn.Module):
         )
         self.proj_out = nn.Linear(channels, channels)
 
-    def forward(self, x, context=None):
+    def forward(self, x, context=None, key_mask=None):
         B, C, H, W = x.shape
         h = self.norm(x).permute(0, 2, 3, 1).reshape(B, H * W, C)
         h = self.proj_in(h)
         for blk in self.blocks:
-            h = blk(h, context)
+            h = blk(h, context, key_mask)
         h = self.proj_out(h)
         return x + h.reshape(B, H, W, C).permute(0, 3, 1, 2)
 
@@ -166,12 +169,12 @@ class _Seq(nn.Module):
         super().__init__()
         self.mods = nn.ModuleList(mods)
 
-    def forward(self, x, emb, context):
+    def forward(self, x, emb, context, key_mask=None):
         for m in self.mods:
             if isinstance(m, ResBlock):
                 x = m(x, emb)
             elif isinstance(m, SpatialTransformer):
-                x = m(x, context)
+                x = m(x, context, key_mask)
             else:
                 x = m(x)
         return x
@@ -241,7 +244,8 @@ class SDUNet(nn.Module):
         self.out_conv = nn.Conv2d(ch, cfg.out_channels, 3, padding=1)
 
     @torch.no_grad()
-    def forward(self, x, timesteps, context=None, y=None, **kwargs):
+    def forward(self, x, timesteps, context=None, y=None,
+                attention_mask=None, **kwargs):
         cfg = self.cfg
         emb = self.time_embed(
             ops.timestep_embedding(timesteps, cfg.model_channels).to(x.dtype)
@@ -254,13 +258,17 @@ class SDUNet(nn.Module):
         if context is None:
             context = torch.zeros(x.shape[0], 1, cfg.context_dim,
                                   device=x.device, dtype=x.dtype)
+        # one packed mask serves every level: the context length is the same
+        # everywhere
+        km = None if attention_mask is None else \
+            context_key_mask(attention_mask, context)
         h = self.input_conv(x)
         skips = [h]
         for mod in self.down:
-            h = mod(h, emb, context)
+            h = mod(h, emb, context, km)
             skips.append(h)
-        h = self.mid(h, emb, context)
+        h = self.mid(h, emb, context, km)
         for mod in self.up:
             h = torch.cat([h, skips.pop()], dim=1)
-            h = mod(h, emb, context)
+            h = mod(h, emb, context, km)
         return self.out_conv(self.out_norm(h))

@@ -16,7 +16,13 @@ import torch
 from torch import nn
 
 from .. import ops
-from .layers import FusedMLP, MLPEmbedder, QKNorm, ln_mod_into
+from .layers import (
+    FusedMLP,
+    MLPEmbedder,
+    QKNorm,
+    context_key_mask,
+    ln_mod_into,
+)
 
 
 def rope_3d_table(f: int, h: int, w: int, axes_dim: Tuple[int, ...],
@@ -49,8 +55,10 @@ class WanBlock(nn.Module):
         self.cross_proj = nn.Linear(dim, dim)
         self.ffn = FusedMLP(dim, ffn_dim, dim)
 
-    def forward(self, x, e, context, pe):
+    def forward(self, x, e, context, pe, key_mask=None):
         # e: [B, 6, dim] time-modulation; learned bias added per block
+        # key_mask: optional ops.KeyMask over the context tokens — masks the
+        # cross-attention only; the space-time self-attention stays unmasked
         m = (e + self.mod).unbind(dim=1)  # 6 x [B, dim]
         shift1, scale1, gate1, shift2, scale2, gate2 = m
 
@@ -71,7 +79,8 @@ class WanBlock(nn.Module):
         k = self.cross_k(context).unflatten(-1, (H, -1))
         v = self.cross_v(context).unflatten(-1, (H, -1))
         x = x + self.cross_proj(
-            ops.attention_bshd(q, k, v, self.scale).flatten(2)
+            ops.attention_bshd(q, k, v, self.scale,
+                               key_mask=key_mask).flatten(2)
         )
 
         return ops.gate_residual(
@@ -155,7 +164,8 @@ class WanDiT(nn.Module):
         return pe
 
     @torch.no_grad()
-    def forward(self, x, timesteps, context=None, image_cond=None, **kwargs):
+    def forward(self, x, timesteps, context=None, image_cond=None,
+                attention_mask=None, **kwargs):
         cfg = self.cfg
         B, C, F, H, W = x.shape
         pf, ph, pw = cfg.patch_size
@@ -190,8 +200,12 @@ class WanDiT(nn.Module):
         tvec = self.time_in.forward_timestep(timesteps)
         e = self.time_proj(torch.nn.functional.silu(tvec)).view(B, 6, cfg.dim)
         pe = self._pe(f, h, w, x.device)
+        mk = {}
+        if attention_mask is not None:
+            # packed once per forward, shared by every block's cross-attention
+            mk["key_mask"] = context_key_mask(attention_mask, ctx)
         for block in self.transformer_blocks:
-            seq = block(seq, e, ctx, pe)
+            seq = block(seq, e, ctx, pe, **mk)
         shift, scale = self.head_mod(torch.nn.functional.silu(tvec)).chunk(2, dim=-1)
         out = self.head(ops.layer_norm_mod(seq, scale, shift))
         return (

@@ -21,6 +21,7 @@ import importlib.util
 import logging
 import math
 import os
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -161,10 +162,77 @@ def rope_freqs(positions, dim: int, theta: float = 10000.0) -> torch.Tensor:
     return reference.rope_freqs(positions, dim, theta)
 
 
-def attention(q, k, v, scale: Optional[float] = None) -> torch.Tensor:
-    """Flash-style fused attention, layout [B, H, S, D]."""
+@dataclass
+class KeyMask:
+    """A [B, Sk] key-padding mask packed for the masked attention kernels.
+
+    Holds tensors only, so parallel.pipeline's recursive move carries it
+    across devices like any other dataclass argument:
+      mask   the bool mask, True = attend
+      words  [B, ceil(Sk/64)] int64, bit j of word t = key 64*t + j
+      live   [B, ceil(Sk/64)] int32, ascending live-tile indices, compacted
+      nlive  [B] int32
+    On CPU only ``mask`` is set; the reference path needs nothing else.
+    """
+    mask: torch.Tensor
+    words: Optional[torch.Tensor] = None
+    live: Optional[torch.Tensor] = None
+    nlive: Optional[torch.Tensor] = None
+
+
+def pack_key_mask(mask) -> KeyMask:
+    """Pack a [B, Sk] bool/integer key mask (nonzero = attend) once, for
+    any number of attention calls over the same keys.
+
+    Contract of every ``key_mask=`` argument below: only keys are masked;
+    K/V rows at masked keys are don't-care (any bit pattern, NaN included);
+    a batch element with no live key returns zeros. Floating masks raise —
+    additive biases are not supported and 0/1 is never guessed from 0/-inf.
+    """
+    if isinstance(mask, KeyMask):
+        return mask
+    m = reference.as_bool_key_mask(mask)
+    if m.is_cuda:
+        ext = _require_ext("pack_key_mask")
+        if ext is not None:
+            words, live, nlive = ext.pack_key_mask(m)
+            return KeyMask(m, words, live, nlive)
+    return KeyMask(m)
+
+
+def _key_mask_for(key_mask, q) -> KeyMask:
+    km = pack_key_mask(key_mask)
+    if km.mask.device != q.device:
+        raise ValueError(f"key mask on {km.mask.device}, q on {q.device}")
+    if km.mask.shape[0] != q.shape[0]:
+        raise ValueError(f"key mask batch {km.mask.shape[0]} != q batch "
+                         f"{q.shape[0]}")
+    if q.is_cuda and km.words is None:
+        # packed on CPU (or under PA_ALLOW_EAGER) and moved: pack here
+        km = pack_key_mask(km.mask)
+    return km
+
+
+def attention(q, k, v, scale: Optional[float] = None,
+              key_mask=None) -> torch.Tensor:
+    """Flash-style fused attention, layout [B, H, S, D].
+
+    key_mask: optional KeyMask or raw [B, Sk] bool/integer mask (see
+    pack_key_mask for the contract)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if key_mask is not None:
+        km = _key_mask_for(key_mask, q)
+        if q.is_cuda:
+            ext = _require_ext("attn_fwd_masked")
+            if ext is not None:
+                D = q.shape[-1]
+                if q.dtype in _NATIVE16 and D in (64, 128):
+                    return ext.attn_fwd_masked(
+                        q.contiguous(), k.contiguous(), v.contiguous(),
+                        float(scale), km.words, km.live, km.nlive)
+                _unsupported("attn_fwd", f"dtype={q.dtype}, D={D}")
+        return reference.attention(q, k, v, scale, km.mask)
     if q.is_cuda:
         ext = _require_ext("attn_fwd")
         if ext is not None:
@@ -177,13 +245,44 @@ def attention(q, k, v, scale: Optional[float] = None) -> torch.Tensor:
     return reference.attention(q, k, v, scale)
 
 
-def attention_bshd(q, k, v, scale: Optional[float] = None) -> torch.Tensor:
+def _attention_bshd_masked(q, k, v, scale: float, km: KeyMask):
+    if q.is_cuda:
+        ext = _require_ext("attn_fwd_bshd_masked")
+        if ext is not None:
+            D = q.shape[-1]
+            if q.dtype in _NATIVE16 and D in (64, 128):
+                return ext.attn_fwd_bshd_masked(q, k, v, float(scale),
+                                                km.words, km.live, km.nlive)
+            if q.dtype in _NATIVE16 and D < 128:
+                # same zero-pad route as the unmasked op
+                Dp = 64 if D <= 64 else 128
+                pad = (0, Dp - D)
+                out = ext.attn_fwd_bshd_masked(
+                    torch.nn.functional.pad(q, pad),
+                    torch.nn.functional.pad(k, pad),
+                    torch.nn.functional.pad(v, pad),
+                    float(scale), km.words, km.live, km.nlive,
+                )
+                return out[..., :D]
+            _unsupported("attn_fwd_bshd", f"dtype={q.dtype}, D={D}")
+    out = reference.attention(
+        q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3),
+        scale, km.mask,
+    )
+    return out.permute(0, 2, 1, 3)
+
+
+def attention_bshd(q, k, v, scale: Optional[float] = None,
+                   key_mask=None) -> torch.Tensor:
     """Fused attention on [B, S, H, D] (strided views allowed — e.g. slices
     of a fused qkv projection; no transpose/contiguous copies on GPU).
 
     Head dims that are not 64/128 but fit under them (SD1.5's 40/80) are
     zero-padded: padding q/k leaves every softmax score unchanged, padded v
     columns are sliced off the output.
+
+    key_mask: optional KeyMask or raw [B, Sk] bool/integer mask (see
+    pack_key_mask for the contract).
 
     Cost statement: the pad wastes attention FLOPs
     proportional to Dp/D — 60% at D=40->64, 60% at D=80->128 — plus one
@@ -196,6 +295,9 @@ def attention_bshd(q, k, v, scale: Optional[float] = None) -> torch.Tensor:
     """
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if key_mask is not None:
+        return _attention_bshd_masked(q, k, v, scale,
+                                      _key_mask_for(key_mask, q))
     if q.is_cuda:
         ext = _require_ext("attn_fwd_bshd")
         if ext is not None:
@@ -220,12 +322,27 @@ def attention_bshd(q, k, v, scale: Optional[float] = None) -> torch.Tensor:
     return out.permute(0, 2, 1, 3)
 
 
-def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None):
+def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None,
+                         key_mask=None):
     """attention_bshd with per-stream outputs: rows [:split] and [split:]
     land in two contiguous tensors (feeds dual-stream projections with no
-    reshape copies)."""
+    reshape copies). key_mask as in attention_bshd."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
+    if key_mask is not None:
+        km = _key_mask_for(key_mask, q)
+        if q.is_cuda and os.environ.get("PA_ATTN_V3") != "1":
+            ext = _require_ext("attn_fwd_bshd_split_masked")
+            if ext is not None and q.dtype in _NATIVE16 \
+                    and q.shape[-1] in (64, 128):
+                a, b = ext.attn_fwd_bshd_split_masked(
+                    q, k, v, float(scale), int(split),
+                    km.words, km.live, km.nlive)
+                return a, b
+            # as below: head dims under 128 reach the native kernel through
+            # the pad route, anything else is reported by attention_bshd
+        out = _attention_bshd_masked(q, k, v, scale, km)
+        return out[:, :split].contiguous(), out[:, split:].contiguous()
     if q.is_cuda:
         if os.environ.get("PA_ATTN_V3") == "1":
             # the v3 debug kernel has no split-output epilogue: compose

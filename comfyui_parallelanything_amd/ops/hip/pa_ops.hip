@@ -1565,7 +1565,20 @@ __global__ void pack_joint_qkv_kernel(
 // MFMA opcode, the P pack (Elem16<E>::pack2) and the epilogue cast. Every
 // LDS layout, tr read and permlane swap is a 16-bit move and is shared;
 // the mask sentinel, online-softmax state and accumulators stay fp32.
-template <int D, typename E>
+//
+// MASKED (key-padding mask, see pack_key_mask_kernel): the KV loop walks the
+// batch element's compacted list of live tiles instead of 0..n_tiles-1, and
+// the per-key validity test `key < Sk` becomes that key's bit in the tile's
+// 64-bit mask word (bits at or beyond Sk are 0, so the bit implies the
+// bound). A dead tile is never loaded or multiplied — the -1e30/-3e30
+// sentinel arithmetic relies on every processed tile holding at least one
+// live key — and a masked K/V row is staged as zeros, so its contents are
+// don't-care. Trip counts and barriers depend only on the block's batch
+// index, i.e. they are uniform across the block. nlive == 0 skips the loop
+// (prologue included) and the epilogue's inv_l = 0 writes zeros.
+// All of it sits under `if constexpr (MASKED)`; the unmasked instantiations
+// compile to the code they had before the flag existed.
+template <int D, typename E, bool MASKED = false>
 __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     const E* __restrict__ q, const E* __restrict__ k,
     const E* __restrict__ v, E* __restrict__ out,
@@ -1575,7 +1588,10 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     long v_bs, long v_hs, int v_ss,
     long o_bs, long o_hs, int o_ss, int xcd_grid,
     E* __restrict__ out2, int s_split,
-    long o2_bs, long o2_hs, int o2_ss) {
+    long o2_bs, long o2_hs, int o2_ss,
+    const unsigned long long* __restrict__ mask_words = nullptr,
+    const int* __restrict__ mask_live = nullptr,
+    const int* __restrict__ mask_nlive = nullptr) {
     using EL = Elem16<E>;
     constexpr int KVBLK = 64;
     constexpr int WAVES = 8;
@@ -1648,14 +1664,19 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     const float scale2 = scale * PA_LOG2E;
 
     bf16x8 kreg[KVECS], vreg[KVECS];
-    auto issue_tile_loads = [&](int kv0) {
+    // `word` (MASKED only) is the tile's mask word: bit `row` set = stage
+    // the row, clear = stage zeros (covers src >= Sk, whose bits are 0)
+    auto issue_tile_loads = [&](int kv0, unsigned long long word = 0) {
 #pragma unroll
         for (int i = 0; i < KVECS; ++i) {
             const int idx = tid + i * THREADS;
             const int row = idx / (D / 8);
             const int col = (idx % (D / 8)) * 8;
             const int src = kv0 + row;
-            if (src < Sk) {
+            bool stage;
+            if constexpr (MASKED) stage = ((word >> row) & 1ull) != 0;
+            else stage = src < Sk;
+            if (stage) {
                 kreg[i] = *reinterpret_cast<const bf16x8*>(kp + (long)src * k_ss + col);
                 vreg[i] = *reinterpret_cast<const bf16x8*>(vp + (long)src * v_ss + col);
             } else {
@@ -1707,18 +1728,32 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
         }
         __builtin_amdgcn_s_setprio(0);
     };
-    auto softmax_phase = [&](int kv0, f32x16* st, bf16x8* pfrag) {
+    auto softmax_phase = [&](int kv0, f32x16* st, bf16x8* pfrag,
+                             unsigned long long word = 0) {
         // lane-local online softmax (this lane's row = q0 + l32);
         // value (kt, reg) = S[row][key = kt*32 + (reg&3) + 8*(reg>>2) + 4*hi]
         // raw tile max (scale2 > 0 commutes with max), softmax scale fused
         // into the exp2 argument as one FMA per element.
         float mx = -3e30f;
+        // MASKED: this lane's keys are bits 4*hi + (r&3) + 8*(r>>2) of the
+        // word's half kt — one 64-bit shift, then constant bit positions
+        unsigned int wh[2] = {0u, 0u};
+        if constexpr (MASKED) {
+            const unsigned long long wl = word >> (4 * hi);
+            wh[0] = (unsigned int)wl;
+            wh[1] = (unsigned int)(wl >> 32);
+        }
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = kv0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                const float sv = (key < Sk) ? st[kt][r] : -3e30f;
+                bool valid;
+                if constexpr (MASKED)
+                    valid = ((wh[kt] >> ((r & 3) + 8 * (r >> 2))) & 1u) != 0;
+                else
+                    valid = key < Sk;
+                const float sv = valid ? st[kt][r] : -3e30f;
                 st[kt][r] = sv;
                 mx = fmaxf(mx, sv);
             }
@@ -1787,7 +1822,76 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     };
 
     const int n_tiles = (Sk + KVBLK - 1) / KVBLK;
-    if constexpr (DBUF == 2) {
+    if constexpr (MASKED) {
+        // b is uniform across the block, so are nl, every tile index and
+        // every mask word: readfirstlane pins them in SGPRs
+        const int* live_b = mask_live + b * n_tiles;
+        const unsigned long long* words_b = mask_words + b * n_tiles;
+        const int nl = __builtin_amdgcn_readfirstlane(mask_nlive[b]);
+        auto tile_at = [&](int j) {
+            return __builtin_amdgcn_readfirstlane(live_b[j]);
+        };
+        auto word_of = [&](int tile) {
+            const unsigned long long w = words_b[tile];
+            const unsigned int lo =
+                __builtin_amdgcn_readfirstlane((unsigned int)w);
+            const unsigned int hi32 =
+                __builtin_amdgcn_readfirstlane((unsigned int)(w >> 32));
+            return ((unsigned long long)hi32 << 32) | lo;
+        };
+        if constexpr (DBUF == 2) {
+            // same one-barrier pipeline over the live list: live[j+1] is
+            // staged during tile j, live[j+2]'s loads issue before PV
+            if (nl > 0) {
+                const int t0 = tile_at(0);
+                issue_tile_loads(t0 * KVBLK, word_of(t0));
+                write_k_lds(0);
+                write_v_lds(0);
+                if (nl > 1) {
+                    const int t1 = tile_at(1);
+                    issue_tile_loads(t1 * KVBLK, word_of(t1));
+                }
+                __syncthreads();
+            }
+            for (int j = 0; j < nl; ++j) {
+                const int p = j & 1;
+                const int tile = tile_at(j);
+                f32x16 st[2];
+                bf16x8 pfrag[4];
+                qk_phase(p, st);
+                if (j + 1 < nl) write_k_lds(p ^ 1);
+                softmax_phase(tile * KVBLK, st, pfrag, word_of(tile));
+                if (j + 1 < nl) write_v_lds(p ^ 1);
+                if (j + 2 < nl) {
+                    const int t2 = tile_at(j + 2);
+                    issue_tile_loads(t2 * KVBLK, word_of(t2));
+                }
+                pv_phase(p, pfrag);
+                __syncthreads();
+            }
+        } else {
+            if (nl > 0) {
+                const int t0 = tile_at(0);
+                issue_tile_loads(t0 * KVBLK, word_of(t0));
+            }
+            for (int j = 0; j < nl; ++j) {
+                const int tile = tile_at(j);
+                __syncthreads();
+                write_k_lds(0);
+                write_v_lds(0);
+                __syncthreads();
+                if (j + 1 < nl) {
+                    const int t1 = tile_at(j + 1);
+                    issue_tile_loads(t1 * KVBLK, word_of(t1));
+                }
+                f32x16 st[2];
+                bf16x8 pfrag[4];
+                qk_phase(0, st);
+                softmax_phase(tile * KVBLK, st, pfrag, word_of(tile));
+                pv_phase(0, pfrag);
+            }
+        }
+    } else if constexpr (DBUF == 2) {
         // v5a pipelined schedule (measured +4.0% flux / +4.2% long-S over
         // the 2-barrier loop, scripts/attn_v5.hip): double-buffered LDS,
         // ONE barrier per tile; tile t+1's stores land in the other buffer
@@ -2007,9 +2111,82 @@ at::Tensor quant_fp8(at::Tensor x, at::Tensor scale, at::Tensor amax_buf,
     return out;
 }
 
+// ---------------------------------------------------------------------------
+// Key-padding mask pack: [B, Sk] bool (nonzero = attend) -> what the MASKED
+// attention instantiations read.
+//   words[b][t]  bit j = mask[b][64*t + j]; bits at or beyond Sk are 0
+//   live[b][..]  ascending indices of tiles with a nonzero word, compacted
+//                to the front (the tail is zero-filled)
+//   nlive[b]     how many
+// One 256-thread block per batch element (launch-bound, not bandwidth-
+// bound): every wave ballots 64 keys per step into the word, then wave 0
+// compacts 64 tiles per step with a ballot + prefix popcount. Everything
+// stays on the device, so the op is graph-capturable.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pack_key_mask_kernel(
+    const unsigned char* __restrict__ mask, unsigned long long* words,
+    int* __restrict__ live, int* __restrict__ nlive, int Sk, int n_tiles) {
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    const unsigned char* mb = mask + (long)b * Sk;
+    unsigned long long* wb = words + (long)b * n_tiles;
+    int* lb = live + (long)b * n_tiles;
+    for (int t = wid; t < n_tiles; t += 4) {
+        const int key = t * 64 + lane;
+        const bool on = key < Sk && mb[key] != 0;
+        const unsigned long long w = __ballot(on);
+        if (lane == 0) wb[t] = w;
+    }
+    __syncthreads();  // words of this batch element visible to wave 0
+    if (wid != 0) return;
+    int count = 0;
+    for (int base = 0; base < n_tiles; base += 64) {
+        const int t = base + lane;
+        const bool alive = t < n_tiles && wb[t] != 0ull;
+        const unsigned long long m = __ballot(alive);
+        if (alive)
+            lb[count + __popcll(m & ((1ull << lane) - 1ull))] = t;
+        count += __popcll(m);
+    }
+    for (int i = count + lane; i < n_tiles; i += 64) lb[i] = 0;
+    if (lane == 0) nlive[b] = count;
+}
+
+std::vector<at::Tensor> pack_key_mask(at::Tensor mask) {
+    CHECK_GPU(mask);
+    TORCH_CHECK(mask.dim() == 2, "pack_key_mask expects a [B, Sk] mask");
+    TORCH_CHECK(mask.scalar_type() == at::kBool ||
+                    at::isIntegralType(mask.scalar_type(), false),
+                "pack_key_mask: bool or integer mask only (nonzero = attend); "
+                "additive float biases are not supported, got ",
+                mask.scalar_type());
+    // integer masks: nonzero -> true, on the device (no host read)
+    auto mb = (mask.scalar_type() == at::kBool ? mask : mask.ne(0))
+                  .contiguous();
+    const int B = (int)mb.size(0), Sk = (int)mb.size(1);
+    const int n_tiles = (Sk + 63) / 64;
+    auto words = at::empty({B, n_tiles}, mb.options().dtype(at::kLong));
+    auto live = at::empty({B, n_tiles}, mb.options().dtype(at::kInt));
+    auto nlive = at::empty({B}, mb.options().dtype(at::kInt));
+    if (B > 0)
+        hipLaunchKernelGGL(pack_key_mask_kernel, dim3((unsigned)B), dim3(256),
+                           0, cur_stream(),
+                           (const unsigned char*)mb.data_ptr(),
+                           (unsigned long long*)words.data_ptr(),
+                           live.data_ptr<int>(), nlive.data_ptr<int>(), Sk,
+                           n_tiles);
+    return {words, live, nlive};
+}
+
 struct AttnStrides {
     long bs, hs;
     int ss;
+};
+
+// Packed key mask as the MASKED kernels take it (see pack_key_mask).
+struct AttnKeyMask {
+    at::Tensor words, live, nlive;
 };
 
 static AttnStrides strides_of(const at::Tensor& t, int d_axis_check) {
@@ -2019,17 +2196,18 @@ static AttnStrides strides_of(const at::Tensor& t, int d_axis_check) {
 
 static std::vector<at::Tensor> attn_fwd_launch_split(
     at::Tensor q, at::Tensor k, at::Tensor v, double scale, bool bshd,
-    long split);
+    long split, const AttnKeyMask* km = nullptr);
 
 static at::Tensor attn_fwd_launch(at::Tensor q, at::Tensor k, at::Tensor v,
-                                  double scale, bool bshd) {
-    return attn_fwd_launch_split(q, k, v, scale, bshd, -1)[0];
+                                  double scale, bool bshd,
+                                  const AttnKeyMask* km = nullptr) {
+    return attn_fwd_launch_split(q, k, v, scale, bshd, -1, km)[0];
 }
 
 
 static std::vector<at::Tensor> attn_fwd_launch_split(
     at::Tensor q, at::Tensor k, at::Tensor v, double scale, bool bshd,
-    long split) {
+    long split, const AttnKeyMask* km) {
     CHECK_GPU(q);
     TORCH_CHECK(is_elem16(q.scalar_type()),
                 "attn_fwd: bf16 or fp16 only, got ", q.scalar_type());
@@ -2054,6 +2232,29 @@ static std::vector<at::Tensor> attn_fwd_launch_split(
     const int Sk = (int)kc.size(s_ax);
     TORCH_CHECK((int)vc.size(s_ax) == Sk && (int)kc.size(h_ax) == H,
                 "attn: k/v shape mismatch");
+    if (km != nullptr) {
+        const long n_tiles = (Sk + 63) / 64;
+        TORCH_CHECK(km->words.device() == qc.device() &&
+                        km->live.device() == qc.device() &&
+                        km->nlive.device() == qc.device(),
+                    "attn_fwd: key mask must be on q's device");
+        TORCH_CHECK(km->words.scalar_type() == at::kLong &&
+                        km->live.scalar_type() == at::kInt &&
+                        km->nlive.scalar_type() == at::kInt,
+                    "attn_fwd: key mask needs int64 words, int32 live/nlive");
+        TORCH_CHECK(km->words.dim() == 2 && km->live.dim() == 2 &&
+                        km->nlive.dim() == 1 && km->words.size(0) == B &&
+                        km->live.size(0) == B && km->nlive.size(0) == B,
+                    "attn_fwd: key mask batch must equal q's batch (", B, ")");
+        TORCH_CHECK(km->words.size(1) == n_tiles &&
+                        km->live.size(1) == n_tiles,
+                    "attn_fwd: key mask was packed for another Sk (", Sk,
+                    " keys need ", n_tiles, " tiles, got ",
+                    km->words.size(1), ")");
+        TORCH_CHECK(km->words.is_contiguous() && km->live.is_contiguous() &&
+                        km->nlive.is_contiguous(),
+                    "attn_fwd: key mask tensors must be contiguous");
+    }
     const bool do_split = split > 0 && split < S && bshd;
     at::Tensor out = bshd
         ? at::empty({B, do_split ? (int)split : S, H, D}, qc.options())
@@ -2090,6 +2291,9 @@ static std::vector<at::Tensor> attn_fwd_launch_split(
     TORCH_CHECK(!use_v3 || qc.scalar_type() == at::kBFloat16,
                 "attn_fwd: PA_ATTN_V3=1 selects the bf16-only debug kernel; "
                 "got ", qc.scalar_type(), " — unset PA_ATTN_V3 for fp16");
+    TORCH_CHECK(!use_v3 || km == nullptr,
+                "attn_fwd: PA_ATTN_V3=1 selects the debug kernel, which has "
+                "no key mask — unset PA_ATTN_V3 for masked attention");
     if (!use_v3) {
         const long BH = (long)B * H;
         const unsigned nq = (unsigned)((S + 255) / 256);
@@ -2098,7 +2302,20 @@ static std::vector<at::Tensor> attn_fwd_launch_split(
             grid_v4 = dim3((unsigned)(nq * BH), 1);
             xcd_grid = 1;
         }
-        if (D == 128) {
+#define PA_ATTN_MASK_ARGS                                                      \
+    (const unsigned long long*)km->words.data_ptr(),                          \
+    km->live.data_ptr<int>(), km->nlive.data_ptr<int>()
+        if (km != nullptr && D == 128) {
+            PA_WITH_ELEM16(qc.scalar_type(), hipLaunchKernelGGL(
+                HIP_KERNEL_NAME(attn_fwd_v4_kernel<128, E, true>), grid_v4,
+                dim3(512), 0, cur_stream(), PA_ATTN_ARGS_T(E), xcd_grid,
+                (E*)o2p, ssplit, o2_bs, o2_hs, o2_ss, PA_ATTN_MASK_ARGS));
+        } else if (km != nullptr) {
+            PA_WITH_ELEM16(qc.scalar_type(), hipLaunchKernelGGL(
+                HIP_KERNEL_NAME(attn_fwd_v4_kernel<64, E, true>), grid_v4,
+                dim3(512), 0, cur_stream(), PA_ATTN_ARGS_T(E), xcd_grid,
+                (E*)o2p, ssplit, o2_bs, o2_hs, o2_ss, PA_ATTN_MASK_ARGS));
+        } else if (D == 128) {
             PA_WITH_ELEM16(qc.scalar_type(), hipLaunchKernelGGL(
                 HIP_KERNEL_NAME(attn_fwd_v4_kernel<128, E>), grid_v4,
                 dim3(512), 0, cur_stream(), PA_ATTN_ARGS_T(E), xcd_grid,
@@ -2117,6 +2334,7 @@ static std::vector<at::Tensor> attn_fwd_launch_split(
         hipLaunchKernelGGL(attn_fwd_kernel<64>, grid, dim3(512), 0,
                            cur_stream(), PA_ATTN_ARGS);
     }
+#undef PA_ATTN_MASK_ARGS
 #undef PA_ATTN_ARGS
 #undef PA_ATTN_ARGS_T
     if (do_split) return {out, out2};
@@ -2137,6 +2355,27 @@ std::vector<at::Tensor> attn_fwd_bshd_split(at::Tensor q, at::Tensor k,
     return attn_fwd_launch_split(q, k, v, scale, /*bshd=*/true, split);
 }
 
+at::Tensor attn_fwd_masked(at::Tensor q, at::Tensor k, at::Tensor v,
+                           double scale, at::Tensor words, at::Tensor live,
+                           at::Tensor nlive) {
+    const AttnKeyMask km{words, live, nlive};
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/false, &km);
+}
+
+at::Tensor attn_fwd_bshd_masked(at::Tensor q, at::Tensor k, at::Tensor v,
+                                double scale, at::Tensor words,
+                                at::Tensor live, at::Tensor nlive) {
+    const AttnKeyMask km{words, live, nlive};
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, &km);
+}
+
+std::vector<at::Tensor> attn_fwd_bshd_split_masked(
+    at::Tensor q, at::Tensor k, at::Tensor v, double scale, long split,
+    at::Tensor words, at::Tensor live, at::Tensor nlive) {
+    const AttnKeyMask km{words, live, nlive};
+    return attn_fwd_launch_split(q, k, v, scale, /*bshd=*/true, split, &km);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rms_norm", &rms_norm, "RMSNorm (gfx950)",
           py::arg("x"), py::arg("weight") = py::none(), py::arg("eps") = 1e-6);
@@ -2155,6 +2394,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "Fused flash attention fwd on [B,S,H,D] strided views (gfx950)");
     m.def("attn_fwd_bshd_split", &attn_fwd_bshd_split,
           "Attention with per-stream split outputs [B,:split]/[B,split:]");
+    m.def("pack_key_mask", &pack_key_mask,
+          "[B,Sk] bool/int key mask -> (words, live tile list, nlive)");
+    m.def("attn_fwd_masked", &attn_fwd_masked,
+          "attn_fwd with a packed key-padding mask (dead tiles skipped)");
+    m.def("attn_fwd_bshd_masked", &attn_fwd_bshd_masked,
+          "attn_fwd_bshd with a packed key-padding mask");
+    m.def("attn_fwd_bshd_split_masked", &attn_fwd_bshd_split_masked,
+          "attn_fwd_bshd_split with a packed key-padding mask");
     m.def("gelu_tanh", &gelu_tanh, "Vectorized tanh-GELU (gfx950)");
     m.def("gelu_fp8", &gelu_fp8,
           "tanh-GELU with fused e4m3fn quant + delayed scaling (gfx950)");

@@ -100,16 +100,53 @@ def rope_apply(x: torch.Tensor, cs: torch.Tensor) -> torch.Tensor:
     return out.reshape(B, H, S, D).to(dtype)
 
 
+def as_bool_key_mask(mask: torch.Tensor) -> torch.Tensor:
+    """[B, Sk] bool/integer key mask (nonzero = attend) -> bool.
+
+    Floating masks are refused: a float tensor could be a 0/1 mask or a
+    0/-inf additive bias, and guessing wrong silently inverts the mask.
+    """
+    if mask.dtype.is_floating_point or mask.dtype.is_complex:
+        raise ValueError(
+            f"key mask must be bool or integer (nonzero = attend), got "
+            f"{mask.dtype}: additive float biases are not supported")
+    if mask.dim() != 2:
+        raise ValueError(f"key mask must be [B, Sk], got {tuple(mask.shape)}")
+    return mask if mask.dtype == torch.bool else mask != 0
+
+
 def attention(
-    q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None
+    q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None,
+    key_mask: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
-    """Plain attention, [B, H, S, D] -> [B, H, S, D]. fp32 softmax."""
+    """Plain attention, [B, H, S, D] -> [B, H, S, D]. fp32 softmax.
+
+    key_mask: optional [B, Sk] bool/integer, nonzero = attend. Masked K/V
+    rows are don't-care (zeroed before the matmuls, so NaN/Inf there never
+    reaches the result), masked scores go to -inf, and a batch element with
+    no live key gives zeros.
+    """
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     dtype = q.dtype
-    s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
+    if key_mask is None:
+        s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
+        p = torch.softmax(s, dim=-1)
+        return torch.matmul(p, v.float()).to(dtype)
+    m = as_bool_key_mask(key_mask).to(q.device)
+    if m.shape != (q.shape[0], k.shape[2]):
+        raise ValueError(f"key mask {tuple(m.shape)} does not match "
+                         f"[B={q.shape[0]}, Sk={k.shape[2]}]")
+    rows = m[:, None, :, None]                      # [B, 1, Sk, 1]
+    kf = torch.where(rows, k.float(), torch.zeros((), device=k.device))
+    vf = torch.where(rows, v.float(), torch.zeros((), device=v.device))
+    s = torch.matmul(q.float(), kf.transpose(-1, -2)) * scale
+    s = s.masked_fill(~m[:, None, None, :], float("-inf"))
     p = torch.softmax(s, dim=-1)
-    return torch.matmul(p, v.float()).to(dtype)
+    # all keys masked: softmax over all -inf is NaN; the contract is zeros
+    p = torch.where(m.any(dim=1)[:, None, None, None], p,
+                    torch.zeros((), device=p.device))
+    return torch.matmul(p, vf).to(dtype)
 
 
 def timestep_embedding(

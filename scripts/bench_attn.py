@@ -7,7 +7,13 @@ the roofline context. Random data (guide §5.4 rule 25).
 
 --dtype {bf16,fp16} picks the element type of the attention and fused-op
 sections (default bf16); the hipBLASLt reference stays bf16. --attn-only
-stops after the attention section (for dtype A/B runs)."""
+stops after the attention section (for dtype A/B runs).
+
+--key-mask {none,full,lens} runs the attention section with a key-padding
+mask, packed once outside the timed loop as the models do per forward:
+full = all keys live (the masked kernel's overhead against none), lens = the
+first --live-keys keys of every batch element live (tile skipping). TF/s
+always counts the dense Sq x Sk problem, so it is comparable across modes."""
 import argparse
 import sys
 import time
@@ -29,31 +35,45 @@ def timeit(fn, iters=20, warmup=5):
     return (time.perf_counter() - t0) / iters
 
 
-def attn_flops(B, H, S, D):
-    return 4.0 * B * H * S * S * D  # QK^T + PV, 2 FLOP per MAC
+def attn_flops(B, H, S, D, Sk=None):
+    # QK^T + PV, 2 FLOP per MAC
+    return 4.0 * B * H * S * (S if Sk is None else Sk) * D
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16")
     ap.add_argument("--attn-only", action="store_true")
+    ap.add_argument("--key-mask", choices=("none", "full", "lens"),
+                    default="none")
+    ap.add_argument("--live-keys", type=int, default=64,
+                    help="live keys per batch element for --key-mask lens")
     args = ap.parse_args()
     dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
     assert torch.cuda.is_available()
     dev = "cuda"
-    print(f"== attention ({args.dtype}, random data) ==")
-    for name, (B, H, S, D) in {
-        "flux_b8": (8, 24, 4608, 128),
-        "flux_b1": (1, 24, 4608, 128),
-        "sdxl_mid": (4, 20, 1024, 64),
-        "square_2k": (16, 16, 2048, 128),
+    print(f"== attention ({args.dtype}, random data, "
+          f"key mask: {args.key_mask}) ==")
+    for name, (B, H, S, Sk, D) in {
+        "flux_b8": (8, 24, 4608, 4608, 128),
+        "flux_b1": (1, 24, 4608, 4608, 128),
+        "sdxl_mid": (4, 20, 1024, 1024, 64),
+        "square_2k": (16, 16, 2048, 2048, 128),
+        "zimage_b21": (21, 28, 4352, 4352, 128),  # joint 256 txt + 4096 img
+        "cross_512": (21, 28, 4096, 512, 128),    # padded text context
     }.items():
         q = torch.randn(B, H, S, D, device=dev, dtype=dtype)
-        k = torch.randn_like(q)
-        v = torch.randn_like(q)
-        dt = timeit(lambda: ops.attention(q, k, v), iters=10)
-        tf = attn_flops(B, H, S, D) / dt / 1e12
-        print(f"  {name:10s} B{B} H{H} S{S} D{D}: {dt*1e3:8.2f} ms  {tf:7.1f} TF/s")
+        k = torch.randn(B, H, Sk, D, device=dev, dtype=dtype)
+        v = torch.randn_like(k)
+        km = None
+        if args.key_mask != "none":
+            live = Sk if args.key_mask == "full" else min(args.live_keys, Sk)
+            km = ops.pack_key_mask(
+                (torch.arange(Sk, device=dev) < live).expand(B, Sk))
+        dt = timeit(lambda: ops.attention(q, k, v, key_mask=km), iters=10)
+        tf = attn_flops(B, H, S, D, Sk) / dt / 1e12
+        print(f"  {name:10s} B{B} H{H} S{S} Sk{Sk} D{D}: {dt*1e3:8.2f} ms  "
+              f"{tf:7.1f} TF/s")
     if args.attn_only:
         return
 
