@@ -213,6 +213,41 @@ def _key_mask_for(key_mask, q) -> KeyMask:
     return km
 
 
+def _attn_native(q, k, v, scale: float, km: Optional[KeyMask], bshd: bool,
+                 split: Optional[int] = None):
+    """One attention call on the native kernels: (output, None), or
+    (None, why) when the call is not covered. ``why`` is None when there
+    is no extension to ask (PA_ALLOW_EAGER).
+
+    Picks ext.attn_fwd[_bshd][_split][_masked]. Head dims 64/128 run as they
+    are; other 16-bit head dims under 128 are zero-padded up, on the plain
+    BSHD op only (see attention_bshd)."""
+    name = ("attn_fwd" + ("_bshd" if bshd else "")
+            + ("_split" if split is not None else "")
+            + ("_masked" if km is not None else ""))
+    ext = _require_ext(name)
+    if ext is None:
+        return None, None
+    fn = getattr(ext, name)
+    args = (float(scale),)
+    if split is not None:
+        args += (int(split),)
+    if km is not None:
+        args += (km.words, km.live, km.nlive)
+    D = q.shape[-1]
+    if q.dtype in _NATIVE16 and D in (64, 128):
+        if not bshd:
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        return fn(q, k, v, *args), None
+    if q.dtype in _NATIVE16 and D < 128 and bshd and split is None:
+        pad = (0, (64 if D <= 64 else 128) - D)
+        out = fn(torch.nn.functional.pad(q, pad),
+                 torch.nn.functional.pad(k, pad),
+                 torch.nn.functional.pad(v, pad), *args)
+        return out[..., :D], None
+    return None, f"dtype={q.dtype}, D={D}"
+
+
 def attention(q, k, v, scale: Optional[float] = None,
               key_mask=None) -> torch.Tensor:
     """Flash-style fused attention, layout [B, H, S, D].
@@ -221,55 +256,15 @@ def attention(q, k, v, scale: Optional[float] = None,
     pack_key_mask for the contract)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    if key_mask is not None:
-        km = _key_mask_for(key_mask, q)
-        if q.is_cuda:
-            ext = _require_ext("attn_fwd_masked")
-            if ext is not None:
-                D = q.shape[-1]
-                if q.dtype in _NATIVE16 and D in (64, 128):
-                    return ext.attn_fwd_masked(
-                        q.contiguous(), k.contiguous(), v.contiguous(),
-                        float(scale), km.words, km.live, km.nlive)
-                _unsupported("attn_fwd", f"dtype={q.dtype}, D={D}")
-        return reference.attention(q, k, v, scale, km.mask)
+    km = None if key_mask is None else _key_mask_for(key_mask, q)
     if q.is_cuda:
-        ext = _require_ext("attn_fwd")
-        if ext is not None:
-            D = q.shape[-1]
-            if q.dtype in _NATIVE16 and D in (64, 128):
-                return ext.attn_fwd(q.contiguous(), k.contiguous(),
-                                    v.contiguous(), float(scale))
-            _unsupported("attn_fwd", f"dtype={q.dtype}, D={D}")
-            return reference.attention(q, k, v, scale)
-    return reference.attention(q, k, v, scale)
-
-
-def _attention_bshd_masked(q, k, v, scale: float, km: KeyMask):
-    if q.is_cuda:
-        ext = _require_ext("attn_fwd_bshd_masked")
-        if ext is not None:
-            D = q.shape[-1]
-            if q.dtype in _NATIVE16 and D in (64, 128):
-                return ext.attn_fwd_bshd_masked(q, k, v, float(scale),
-                                                km.words, km.live, km.nlive)
-            if q.dtype in _NATIVE16 and D < 128:
-                # same zero-pad route as the unmasked op
-                Dp = 64 if D <= 64 else 128
-                pad = (0, Dp - D)
-                out = ext.attn_fwd_bshd_masked(
-                    torch.nn.functional.pad(q, pad),
-                    torch.nn.functional.pad(k, pad),
-                    torch.nn.functional.pad(v, pad),
-                    float(scale), km.words, km.live, km.nlive,
-                )
-                return out[..., :D]
-            _unsupported("attn_fwd_bshd", f"dtype={q.dtype}, D={D}")
-    out = reference.attention(
-        q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3),
-        scale, km.mask,
-    )
-    return out.permute(0, 2, 1, 3)
+        out, why = _attn_native(q, k, v, scale, km, bshd=False)
+        if out is not None:
+            return out
+        if why is not None:
+            _unsupported("attn_fwd", why)
+    return reference.attention(q, k, v, scale,
+                               None if km is None else km.mask)
 
 
 def attention_bshd(q, k, v, scale: Optional[float] = None,
@@ -295,29 +290,16 @@ def attention_bshd(q, k, v, scale: Optional[float] = None,
     """
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    if key_mask is not None:
-        return _attention_bshd_masked(q, k, v, scale,
-                                      _key_mask_for(key_mask, q))
+    km = None if key_mask is None else _key_mask_for(key_mask, q)
     if q.is_cuda:
-        ext = _require_ext("attn_fwd_bshd")
-        if ext is not None:
-            D = q.shape[-1]
-            if q.dtype in _NATIVE16 and D in (64, 128):
-                return ext.attn_fwd_bshd(q, k, v, float(scale))
-            if q.dtype in _NATIVE16 and D < 128:
-                Dp = 64 if D <= 64 else 128
-                pad = (0, Dp - D)
-                out = ext.attn_fwd_bshd(
-                    torch.nn.functional.pad(q, pad),
-                    torch.nn.functional.pad(k, pad),
-                    torch.nn.functional.pad(v, pad),
-                    float(scale),
-                )
-                return out[..., :D]
-            _unsupported("attn_fwd_bshd", f"dtype={q.dtype}, D={D}")
+        out, why = _attn_native(q, k, v, scale, km, bshd=True)
+        if out is not None:
+            return out
+        if why is not None:
+            _unsupported("attn_fwd_bshd", why)
     out = reference.attention(
         q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3),
-        scale,
+        scale, None if km is None else km.mask,
     )
     return out.permute(0, 2, 1, 3)
 
@@ -329,40 +311,25 @@ def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None,
     reshape copies). key_mask as in attention_bshd."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    if key_mask is not None:
-        km = _key_mask_for(key_mask, q)
-        if q.is_cuda and os.environ.get("PA_ATTN_V3") != "1":
-            ext = _require_ext("attn_fwd_bshd_split_masked")
-            if ext is not None and q.dtype in _NATIVE16 \
-                    and q.shape[-1] in (64, 128):
-                a, b = ext.attn_fwd_bshd_split_masked(
-                    q, k, v, float(scale), int(split),
-                    km.words, km.live, km.nlive)
-                return a, b
-            # as below: head dims under 128 reach the native kernel through
-            # the pad route, anything else is reported by attention_bshd
-        out = _attention_bshd_masked(q, k, v, scale, km)
-        return out[:, :split].contiguous(), out[:, split:].contiguous()
-    if q.is_cuda:
-        if os.environ.get("PA_ATTN_V3") == "1":
-            # the v3 debug kernel has no split-output epilogue: compose
-            # via the plain kernel + slices so the escape hatch covers
-            # the whole op surface
-            out = attention_bshd(q, k, v, scale)
-            return out[:, :split].contiguous(), out[:, split:].contiguous()
-        ext = _require_ext("attn_fwd_bshd_split")
-        if ext is not None and q.dtype in _NATIVE16 \
-                and q.shape[-1] in (64, 128):
-            a, b = ext.attn_fwd_bshd_split(q, k, v, float(scale), int(split))
+    km = None if key_mask is None else _key_mask_for(key_mask, q)
+    # the v3 debug kernel has no split-output epilogue: under PA_ATTN_V3 the
+    # op composes from the plain kernel + slices, so the escape hatch covers
+    # the whole op surface
+    if q.is_cuda and os.environ.get("PA_ATTN_V3") != "1":
+        out, why = _attn_native(q, k, v, scale, km, bshd=True, split=split)
+        if out is not None:
+            a, b = out
             return a, b
         # 16-bit head dims below 128 still run the native kernel through
         # attention_bshd's zero-pad route (only the split epilogue is
-        # composed from slices) — that is no reference-path fallback
-        if not (ext is not None and q.dtype in _NATIVE16
-                and q.shape[-1] < 128):
+        # composed from slices) — that is no reference-path fallback.
+        # Anything else is reported here (unmasked) and by attention_bshd.
+        padded = (why is not None and q.dtype in _NATIVE16
+                  and q.shape[-1] < 128)
+        if km is None and not padded:
             _unsupported("attn_fwd_bshd_split",
                          f"dtype={q.dtype}, D={q.shape[-1]}")
-    out = attention_bshd(q, k, v, scale)
+    out = attention_bshd(q, k, v, scale, km)
     return out[:, :split].contiguous(), out[:, split:].contiguous()
 
 

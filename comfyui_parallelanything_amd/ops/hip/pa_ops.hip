@@ -323,27 +323,77 @@ __global__ void layer_norm_mod_vec_kernel(const E* __restrict__ x,
 }
 
 
+// ---- fp8 (e4m3fn) emit: shared by layer_norm_mod_fp8_kernel,
+// gelu_fp8_kernel and quant_fp8_bf16_kernel ---------------------------------
+// Delayed scaling: each of the three quantizes with the scale it finds in
+// scale[0] and maxes its |value| into amax_buf[0]. Nothing else happens in
+// the kernel: the stream-ordered fp8_scale_finalize_kernel launched right
+// after it snapshots that scale into scale_used[0], decays the amax and
+// writes the next call's scale.
+
+// Eight values f(0..7) -> clamp(f * inv_s) to the e4m3 range, cast, one
+// 8-byte store at out[at]. f is a callable, not an array, and the address
+// is formed here, so the inlined code keeps the per-element order (value,
+// amax, cast, ..., address, store) the kernels were tuned with: an array
+// argument or a precomputed pointer cost 1-3 VGPRs in two of the kernels.
+template <typename F>
+PA_DEV void store_fp8x8(unsigned char* out, long at, float inv_s, F&& f) {
+    unsigned char pack[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float q = fminf(fmaxf(f(j) * inv_s, -448.f), 448.f);
+        // OCP e4m3fn cast (gfx950 format; NOT fnuz)
+        pack[j] = (unsigned char)__hip_cvt_float_to_fp8(q, __HIP_SATFINITE,
+                                                        __HIP_E4M3);
+    }
+    *reinterpret_cast<unsigned long long*>(&out[at]) =
+        *reinterpret_cast<unsigned long long*>(pack);
+}
+
+// Block amax -> amax_buf[0], CONDITIONAL atomicMax: thread 0 reads the
+// global value plainly first and issues the atomic only when this block
+// holds a new maximum, so a launch of thousands of blocks does a handful of
+// real atomics. The round-2 fp8k A/B measured the scheme this replaced — a
+// per-block counter chain (4096 serialized atomicAdds) for last-block
+// detection — at up to ~30% of the whole kernel. Deterministic: atomicMax
+// is order-independent and the finalize kernel sees the final amax.
+// `scratch` holds one float per wave; every thread of the block calls this.
+PA_DEV void block_amax_to_global(float local_amax, float* scratch,
+                                 float* amax_buf) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        local_amax = fmaxf(local_amax, __shfl_xor(local_amax, off, 64));
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    if (lane == 0) scratch[wid] = local_amax;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float m = 0.f;
+        for (int i = 0; i < (int)(blockDim.x / 64); ++i)
+            m = fmaxf(m, scratch[i]);
+        if (m > amax_buf[0])
+            atomicMax(reinterpret_cast<unsigned int*>(amax_buf),
+                      __float_as_uint(m));
+    }
+}
+
 // AdaLN-modulated LayerNorm with the bf16 -> fp8(e4m3fn) cast fused into
 // the normalize pass (fp8 serving mode): kills the standalone quant_fp8
 // pass per projection (one HBM round-trip of [B,S,D] saved per call).
-// Delayed scaling identical to quant_fp8_bf16_kernel: quantizes with
-// qscale[0], atomically maxes |out| into amax_buf[0], the LAST block
-// (amax_buf[1] = counter) writes the NEXT call's scale and snapshots the
-// used scale into scale_used[0] for _scaled_mm.
+// Quantizes with qscale[0] and maxes |out| into amax_buf[0] (see above).
 __global__ void layer_norm_mod_fp8_kernel(
     const bf16* __restrict__ x, const bf16* __restrict__ scale_m,
     const bf16* __restrict__ shift, unsigned char* __restrict__ out,
     long n_rows, int S, int D, float eps, float* __restrict__ qscale,
-    float* __restrict__ amax_buf, float* scale_used) {
+    float* __restrict__ amax_buf) {
     const int DV = D / 8;
     __shared__ float scratch[8];
-    const float s_entry = qscale[0];
-    const float inv_s = 1.0f / s_entry;
+    const float inv_s = 1.0f / qscale[0];
 
-    // Block-per-row like the bf16 LN kernel (6+ TB/s): with the counter
-    // chain gone and the amax atomic CONDITIONAL, a 37k-block launch does
-    // only a handful of real atomics — the earlier grid-stride detour
-    // (latency-bound at 2.3 TB/s) is no longer needed.
+    // Block-per-row like the bf16 LN kernel (6+ TB/s): with the amax atomic
+    // CONDITIONAL, a 37k-block launch does only a handful of real atomics —
+    // the earlier grid-stride detour (latency-bound at 2.3 TB/s) is no
+    // longer needed.
     float local_amax = 0.f;
     const long row = blockIdx.x;
     if (row < n_rows) {
@@ -369,43 +419,18 @@ __global__ void layer_norm_mod_fp8_kernel(
         const float rstd = rsqrtf(var + eps);
         for (int i = threadIdx.x; i < DV; i += blockDim.x) {
             short8 v = xr[i], a = sc[i], c = sh[i];
-            unsigned char pack[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
+            store_fp8x8(out, row * (long)D + i * 8, inv_s, [&](int j) {
                 float f = (bf2f(__ushort_as_bfloat16((unsigned short)v[j])) - mean) * rstd;
                 f = f * (1.f + bf2f(__ushort_as_bfloat16((unsigned short)a[j]))) +
                     bf2f(__ushort_as_bfloat16((unsigned short)c[j]));
                 local_amax = fmaxf(local_amax, fabsf(f));
-                float qv = fminf(fmaxf(f * inv_s, -448.f), 448.f);
-                pack[j] = (unsigned char)__hip_cvt_float_to_fp8(
-                    qv, __HIP_SATFINITE, __HIP_E4M3);
-            }
-            *reinterpret_cast<unsigned long long*>(
-                &out[row * (long)D + i * 8]) =
-                *reinterpret_cast<unsigned long long*>(pack);
+                return f;
+            });
         }
     }
     // scratch reuse: stragglers may still read the reduce broadcast
     __syncthreads();
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        local_amax = fmaxf(local_amax, __shfl_xor(local_amax, off, 64));
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    if (lane == 0) scratch[wid] = local_amax;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float m = 0.f;
-        for (int i = 0; i < (int)(blockDim.x / 64); ++i)
-            m = fmaxf(m, scratch[i]);
-        // conditional atomicMax only; decay/scale/snapshot run in the
-        // stream-ordered fp8_scale_finalize_kernel (counter chain removed
-        // — see quant_fp8_bf16_kernel note)
-        if (m > amax_buf[0])
-            atomicMax(reinterpret_cast<unsigned int*>(amax_buf),
-                      __float_as_uint(m));
-    }
-    (void)s_entry;
+    block_amax_to_global(local_amax, scratch, amax_buf);
 }
 
 // 16-bit fast path: 8-wide gated residual
@@ -438,22 +463,17 @@ __global__ void gate_residual_vec_kernel(const E* __restrict__ res,
 }
 
 
-// Vectorized tanh-GELU (bf16 short8): the MLP activation between the two
-// hipBLASLt GEMMs ([B, S, 4*hidden] tensors; memory-bound).
 // tanh-GELU with the bf16 -> e4m3fn cast fused (fp8 serving mode): the
 // MLP-down projection consumes the GELU output, so emitting fp8 directly
-// removes its standalone quant pass (same delayed-scaling epilogue as
-// quant_fp8: one amax atomic + counter hit per block, last block writes
-// the next scale and snapshots the used one).
+// removes its standalone quant pass. Quantizes with scale[0] and maxes
+// |gelu| into amax_buf[0], like quant_fp8_bf16_kernel (see "fp8 emit").
 __global__ void gelu_fp8_kernel(const bf16* __restrict__ x,
                                 unsigned char* __restrict__ out, long total8,
                                 float* __restrict__ scale,
-                                float* __restrict__ amax_buf,
-                                float* scale_used) {
+                                float* __restrict__ amax_buf) {
     const long stride = (long)gridDim.x * blockDim.x;
     const short8* xv = reinterpret_cast<const short8*>(x);
-    const float s_entry = scale[0];
-    const float inv_s = 1.0f / s_entry;
+    const float inv_s = 1.0f / scale[0];
     float local_amax = 0.f;
     // 4-deep ILP: four independent loads in flight before the compute
     // (fp8k A/B: +5% on this pattern)
@@ -469,9 +489,7 @@ __global__ void gelu_fp8_kernel(const bf16* __restrict__ x,
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
             if (idx[h] >= total8) break;
-            unsigned char pack[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
+            store_fp8x8(out, idx[h] * 8, inv_s, [&](int j) {
                 const float f =
                     bf2f(__ushort_as_bfloat16((unsigned short)v[h][j]));
                 const float c =
@@ -485,37 +503,17 @@ __global__ void gelu_fp8_kernel(const bf16* __restrict__ x,
                 const float r = __builtin_amdgcn_rcpf(1.f + En);
                 const float g = f * (c >= 0.f ? r : 1.f - r);
                 local_amax = fmaxf(local_amax, fabsf(g));
-                const float qv = fminf(fmaxf(g * inv_s, -448.f), 448.f);
-                pack[j] = (unsigned char)__hip_cvt_float_to_fp8(
-                    qv, __HIP_SATFINITE, __HIP_E4M3);
-            }
-            *reinterpret_cast<unsigned long long*>(&out[idx[h] * 8]) =
-                *reinterpret_cast<unsigned long long*>(pack);
+                return g;
+            });
         }
     }
     __shared__ float scratch[8];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        local_amax = fmaxf(local_amax, __shfl_xor(local_amax, off, 64));
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    if (lane == 0) scratch[wid] = local_amax;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float m = 0.f;
-        for (int i = 0; i < (int)(blockDim.x / 64); ++i)
-            m = fmaxf(m, scratch[i]);
-        // conditional atomicMax only; decay/scale/snapshot run in the
-        // stream-ordered fp8_scale_finalize_kernel (counter chain removed
-        // — see quant_fp8_bf16_kernel note)
-        if (m > amax_buf[0])
-            atomicMax(reinterpret_cast<unsigned int*>(amax_buf),
-                      __float_as_uint(m));
-    }
-    (void)s_entry;
+    block_amax_to_global(local_amax, scratch, amax_buf);
 }
 
 
+// Vectorized tanh-GELU (16-bit short8): the MLP activation between the two
+// hipBLASLt GEMMs ([B, S, 4*hidden] tensors; memory-bound).
 template <typename E>
 __global__ void gelu_tanh_vec_kernel(const E* __restrict__ x,
                                      E* __restrict__ out, long total8,
@@ -781,12 +779,10 @@ __global__ void quant_fp8_bf16_kernel(const bf16* __restrict__ x,
                                       unsigned char* __restrict__ out,
                                       float* __restrict__ scale,
                                       float* __restrict__ amax_buf,
-                                      float* scale_used,  // may alias scale
-                                      long total8, int fuse_scale) {
+                                      long total8) {
     const long stride = (long)gridDim.x * blockDim.x;
     const short8* xv = reinterpret_cast<const short8*>(x);
-    const float s_entry = scale[0];
-    const float inv_s = 1.0f / s_entry;
+    const float inv_s = 1.0f / scale[0];
     float local_amax = 0.f;
     // 4-deep load ILP (fp8k A/B: +5% on the 16B-load/8B-store pattern)
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total8;
@@ -801,47 +797,16 @@ __global__ void quant_fp8_bf16_kernel(const bf16* __restrict__ x,
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
             if (idx[h] >= total8) break;
-            unsigned char pack[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float f = bf2f(__ushort_as_bfloat16((unsigned short)v[h][j]));
+            store_fp8x8(out, idx[h] * 8, inv_s, [&](int j) {
+                const float f =
+                    bf2f(__ushort_as_bfloat16((unsigned short)v[h][j]));
                 local_amax = fmaxf(local_amax, fabsf(f));
-                float q = f * inv_s;
-                q = fminf(fmaxf(q, -448.f), 448.f);
-                // OCP e4m3fn cast (gfx950 format; NOT fnuz)
-                pack[j] = (unsigned char)__hip_cvt_float_to_fp8(
-                    q, __HIP_SATFINITE, __HIP_E4M3);
-            }
-            *reinterpret_cast<unsigned long long*>(&out[idx[h] * 8]) =
-                *reinterpret_cast<unsigned long long*>(pack);
+                return f;
+            });
         }
     }
-    // block amax -> global, CONDITIONAL atomicMax: plain read first, the
-    // atomic only when this block holds a new maximum. The round-2 fp8k
-    // A/B measured the old per-block counter chain (4096 serialized
-    // atomicAdds for last-block detection) at up to ~30% of the whole
-    // kernel; decay/scale/snapshot moved to the stream-ordered
-    // fp8_scale_finalize_kernel launched right after (deterministic:
-    // atomicMax is order-independent, finalize sees the final amax).
     __shared__ float scratch[8];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        local_amax = fmaxf(local_amax, __shfl_xor(local_amax, off, 64));
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    if (lane == 0) scratch[wid] = local_amax;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float m = 0.f;
-        for (int i = 0; i < (int)(blockDim.x / 64); ++i)
-            m = fmaxf(m, scratch[i]);
-        if (m > amax_buf[0])
-            atomicMax(reinterpret_cast<unsigned int*>(amax_buf),
-                      __float_as_uint(m));
-    }
-    (void)s_entry;
-    (void)fuse_scale;
-    (void)scale_used;
+    block_amax_to_global(local_amax, scratch, amax_buf);
 }
 
 
@@ -1161,6 +1126,16 @@ static bool is_elem16(at::ScalarType t) {
         else { using E = _Float16; __VA_ARGS__; }                             \
     } while (0)
 
+// Second half of every fp8-emitting op: runs after the quantizing kernel on
+// the same stream (see fp8_scale_finalize_kernel).
+static void fp8_scale_finalize(at::Tensor& scale, at::Tensor& amax_buf,
+                               at::Tensor& scale_used) {
+    hipLaunchKernelGGL(fp8_scale_finalize_kernel, dim3(1), dim3(1), 0,
+                       cur_stream(), scale.data_ptr<float>(),
+                       amax_buf.data_ptr<float>(),
+                       scale_used.data_ptr<float>());
+}
+
 at::Tensor rms_norm(at::Tensor x, std::optional<at::Tensor> w, double eps) {
     CHECK_GPU(x);
     auto xc = x.contiguous();
@@ -1257,12 +1232,8 @@ at::Tensor layer_norm_mod_fp8(at::Tensor x, at::Tensor scale, at::Tensor shift,
                        (const bf16*)sc.data_ptr(), (const bf16*)sh.data_ptr(),
                        (unsigned char*)out.data_ptr(), n_rows, S, D,
                        (float)eps, qscale.data_ptr<float>(),
-                       amax_buf.data_ptr<float>(),
-                       scale_used.data_ptr<float>());
-    hipLaunchKernelGGL(fp8_scale_finalize_kernel, dim3(1), dim3(1), 0,
-                       cur_stream(), qscale.data_ptr<float>(),
-                       amax_buf.data_ptr<float>(),
-                       scale_used.data_ptr<float>());
+                       amax_buf.data_ptr<float>());
+    fp8_scale_finalize(qscale, amax_buf, scale_used);
     return out;
 }
 
@@ -1573,11 +1544,11 @@ __global__ void pack_joint_qkv_kernel(
 // bound). A dead tile is never loaded or multiplied — the -1e30/-3e30
 // sentinel arithmetic relies on every processed tile holding at least one
 // live key — and a masked K/V row is staged as zeros, so its contents are
-// don't-care. Trip counts and barriers depend only on the block's batch
-// index, i.e. they are uniform across the block. nlive == 0 skips the loop
-// (prologue included) and the epilogue's inv_l = 0 writes zeros.
-// All of it sits under `if constexpr (MASKED)`; the unmasked instantiations
-// compile to the code they had before the flag existed.
+// don't-care. nlive == 0 skips the loop (prologue included) and the
+// epilogue's inv_l = 0 writes zeros. Both variants run the same KV loops
+// (see "KV loop" in the body); `if constexpr (MASKED)` only picks where the
+// trip count, the tile index and the mask word come from, and the unmasked
+// instantiations compile to the code they had before the flag existed.
 template <int D, typename E, bool MASKED = false>
 __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     const E* __restrict__ q, const E* __restrict__ k,
@@ -1821,113 +1792,97 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
         __builtin_amdgcn_s_setprio(0);
     };
 
+    // ---- KV loop ----------------------------------------------------------
+    // One loop per schedule, written over three block-uniform accessors so
+    // the masked and unmasked instantiations share it:
+    //   nt          trip count: nlive[b] (MASKED) or n_tiles
+    //   tile_at(j)  j-th tile to process: live[b][j] (MASKED) or j
+    //   word_of(t)  tile t's 64-bit mask word (MASKED) or 0 (ignored)
+    // b is uniform across the block, so are nt, every tile index and every
+    // mask word: readfirstlane pins them in SGPRs, and trip counts and
+    // barriers stay block-uniform. With MASKED, nt == 0 skips the prologue's
+    // loads, LDS writes and barrier too; the unmasked prologue is
+    // unconditional, as it was before the flag existed.
     const int n_tiles = (Sk + KVBLK - 1) / KVBLK;
-    if constexpr (MASKED) {
-        // b is uniform across the block, so are nl, every tile index and
-        // every mask word: readfirstlane pins them in SGPRs
-        const int* live_b = mask_live + b * n_tiles;
-        const unsigned long long* words_b = mask_words + b * n_tiles;
-        const int nl = __builtin_amdgcn_readfirstlane(mask_nlive[b]);
-        auto tile_at = [&](int j) {
+    const int* live_b = MASKED ? mask_live + b * n_tiles : nullptr;
+    const unsigned long long* words_b =
+        MASKED ? mask_words + b * n_tiles : nullptr;
+    const int nt =
+        MASKED ? __builtin_amdgcn_readfirstlane(mask_nlive[b]) : n_tiles;
+    auto tile_at = [&](int j) {
+        if constexpr (MASKED)
             return __builtin_amdgcn_readfirstlane(live_b[j]);
-        };
-        auto word_of = [&](int tile) {
+        else
+            return j;
+    };
+    auto word_of = [&](int tile) -> unsigned long long {
+        if constexpr (MASKED) {
             const unsigned long long w = words_b[tile];
             const unsigned int lo =
                 __builtin_amdgcn_readfirstlane((unsigned int)w);
             const unsigned int hi32 =
                 __builtin_amdgcn_readfirstlane((unsigned int)(w >> 32));
             return ((unsigned long long)hi32 << 32) | lo;
-        };
-        if constexpr (DBUF == 2) {
-            // same one-barrier pipeline over the live list: live[j+1] is
-            // staged during tile j, live[j+2]'s loads issue before PV
-            if (nl > 0) {
-                const int t0 = tile_at(0);
-                issue_tile_loads(t0 * KVBLK, word_of(t0));
-                write_k_lds(0);
-                write_v_lds(0);
-                if (nl > 1) {
-                    const int t1 = tile_at(1);
-                    issue_tile_loads(t1 * KVBLK, word_of(t1));
-                }
-                __syncthreads();
-            }
-            for (int j = 0; j < nl; ++j) {
-                const int p = j & 1;
-                const int tile = tile_at(j);
-                f32x16 st[2];
-                bf16x8 pfrag[4];
-                qk_phase(p, st);
-                if (j + 1 < nl) write_k_lds(p ^ 1);
-                softmax_phase(tile * KVBLK, st, pfrag, word_of(tile));
-                if (j + 1 < nl) write_v_lds(p ^ 1);
-                if (j + 2 < nl) {
-                    const int t2 = tile_at(j + 2);
-                    issue_tile_loads(t2 * KVBLK, word_of(t2));
-                }
-                pv_phase(p, pfrag);
-                __syncthreads();
-            }
         } else {
-            if (nl > 0) {
-                const int t0 = tile_at(0);
-                issue_tile_loads(t0 * KVBLK, word_of(t0));
-            }
-            for (int j = 0; j < nl; ++j) {
-                const int tile = tile_at(j);
-                __syncthreads();
-                write_k_lds(0);
-                write_v_lds(0);
-                __syncthreads();
-                if (j + 1 < nl) {
-                    const int t1 = tile_at(j + 1);
-                    issue_tile_loads(t1 * KVBLK, word_of(t1));
-                }
-                f32x16 st[2];
-                bf16x8 pfrag[4];
-                qk_phase(0, st);
-                softmax_phase(tile * KVBLK, st, pfrag, word_of(tile));
-                pv_phase(0, pfrag);
-            }
+            return 0ull;
         }
-    } else if constexpr (DBUF == 2) {
+    };
+    // (the loads are written out at each site: wrapping tile_at + word_of +
+    // issue_tile_loads in one more lambda reorders the unmasked code)
+    if constexpr (DBUF == 2) {
         // v5a pipelined schedule (measured +4.0% flux / +4.2% long-S over
         // the 2-barrier loop, scripts/attn_v5.hip): double-buffered LDS,
-        // ONE barrier per tile; tile t+1's stores land in the other buffer
+        // ONE barrier per tile; tile j+1's stores land in the other buffer
         // interleaved where the LDS port is idle (K after QK^T, V after
-        // softmax); tile t+2's global loads issue before PV.
-        issue_tile_loads(0);
-        write_k_lds(0);
-        write_v_lds(0);
-        if (n_tiles > 1) issue_tile_loads(KVBLK);
-        __syncthreads();
-        for (int t = 0; t < n_tiles; ++t) {
-            const int p = t & 1;
+        // softmax); tile j+2's global loads issue before PV.
+        if (!MASKED || nt > 0) {
+            const int t0 = tile_at(0);
+            issue_tile_loads(t0 * KVBLK, word_of(t0));
+            write_k_lds(0);
+            write_v_lds(0);
+            if (nt > 1) {
+                const int t1 = tile_at(1);
+                issue_tile_loads(t1 * KVBLK, word_of(t1));
+            }
+            __syncthreads();
+        }
+        for (int j = 0; j < nt; ++j) {
+            const int p = j & 1;
+            const int tile = tile_at(j);
             f32x16 st[2];
             bf16x8 pfrag[4];
             qk_phase(p, st);
-            if (t + 1 < n_tiles) write_k_lds(p ^ 1);
-            softmax_phase(t * KVBLK, st, pfrag);
-            if (t + 1 < n_tiles) write_v_lds(p ^ 1);
-            if (t + 2 < n_tiles) issue_tile_loads((t + 2) * KVBLK);
+            if (j + 1 < nt) write_k_lds(p ^ 1);
+            softmax_phase(tile * KVBLK, st, pfrag, word_of(tile));
+            if (j + 1 < nt) write_v_lds(p ^ 1);
+            if (j + 2 < nt) {
+                const int t2 = tile_at(j + 2);
+                issue_tile_loads(t2 * KVBLK, word_of(t2));
+            }
             pv_phase(p, pfrag);
             __syncthreads();
         }
     } else {
         // D=64 keeps the v4 2-barrier loop (v5a measured -2.6% there —
         // halved MFMA per tile leaves too little compute to hide stores).
-        issue_tile_loads(0);
-        for (int t = 0; t < n_tiles; ++t) {
+        if (!MASKED || nt > 0) {
+            const int t0 = tile_at(0);
+            issue_tile_loads(t0 * KVBLK, word_of(t0));
+        }
+        for (int j = 0; j < nt; ++j) {
+            const int tile = tile_at(j);
             __syncthreads();
             write_k_lds(0);
             write_v_lds(0);
             __syncthreads();
-            if (t + 1 < n_tiles) issue_tile_loads((t + 1) * KVBLK);
+            if (j + 1 < nt) {
+                const int t1 = tile_at(j + 1);
+                issue_tile_loads(t1 * KVBLK, word_of(t1));
+            }
             f32x16 st[2];
             bf16x8 pfrag[4];
             qk_phase(0, st);
-            softmax_phase(t * KVBLK, st, pfrag);
+            softmax_phase(tile * KVBLK, st, pfrag, word_of(tile));
             pv_phase(0, pfrag);
         }
     }
@@ -1983,12 +1938,8 @@ at::Tensor gelu_fp8(at::Tensor x, at::Tensor scale, at::Tensor amax_buf,
     hipLaunchKernelGGL(gelu_fp8_kernel, dim3(blocks), dim3(256), 0,
                        cur_stream(), (const bf16*)xc.data_ptr(),
                        (unsigned char*)out.data_ptr(), total8,
-                       scale.data_ptr<float>(), amax_buf.data_ptr<float>(),
-                       scale_used.data_ptr<float>());
-    hipLaunchKernelGGL(fp8_scale_finalize_kernel, dim3(1), dim3(1), 0,
-                       cur_stream(), scale.data_ptr<float>(),
-                       amax_buf.data_ptr<float>(),
-                       scale_used.data_ptr<float>());
+                       scale.data_ptr<float>(), amax_buf.data_ptr<float>());
+    fp8_scale_finalize(scale, amax_buf, scale_used);
     return out;
 }
 
@@ -2093,21 +2044,17 @@ at::Tensor quant_fp8(at::Tensor x, at::Tensor scale, at::Tensor amax_buf,
     auto out = at::empty(xc.sizes(), xc.options().dtype(at::kFloat8_e4m3fn));
     const long total8 = xc.numel() / 8;
     const int blocks = (int)std::min<long>((total8 + 255) / 256, 4096);
-    // amax_buf with a second slot (counter) opts into the fused
-    // delayed-scaling epilogue: the kernel itself writes the next scale
-    // into scale[0] and snapshots the scale it quantized with into
-    // scale_used[0] (pass scale_used=scale to skip the snapshot).
-    const int fuse_scale = amax_buf.numel() >= 2 ? 1 : 0;
     hipLaunchKernelGGL(quant_fp8_bf16_kernel, dim3(blocks), dim3(256), 0,
                        cur_stream(), (const bf16*)xc.data_ptr(),
                        (unsigned char*)out.data_ptr(),
                        scale.data_ptr<float>(), amax_buf.data_ptr<float>(),
-                       scale_used.data_ptr<float>(), total8, fuse_scale);
-    if (fuse_scale)
-        hipLaunchKernelGGL(fp8_scale_finalize_kernel, dim3(1), dim3(1), 0,
-                           cur_stream(), scale.data_ptr<float>(),
-                           amax_buf.data_ptr<float>(),
-                           scale_used.data_ptr<float>());
+                       total8);
+    // amax_buf with a second slot (the retired counter) opts into delayed
+    // scaling: the finalize writes the next scale into scale[0] and
+    // snapshots the scale this call quantized with into scale_used[0]
+    // (pass scale_used=scale to skip the snapshot). A one-slot amax_buf
+    // only accumulates the amax.
+    if (amax_buf.numel() >= 2) fp8_scale_finalize(scale, amax_buf, scale_used);
     return out;
 }
 
@@ -2179,33 +2126,60 @@ std::vector<at::Tensor> pack_key_mask(at::Tensor mask) {
     return {words, live, nlive};
 }
 
-struct AttnStrides {
-    long bs, hs;
-    int ss;
-};
-
 // Packed key mask as the MASKED kernels take it (see pack_key_mask).
 struct AttnKeyMask {
     at::Tensor words, live, nlive;
 };
 
-static AttnStrides strides_of(const at::Tensor& t, int d_axis_check) {
-    TORCH_CHECK(t.stride(3) == 1, "attn: last dim must be contiguous");
-    return AttnStrides{t.stride(0), t.stride(d_axis_check), (int)0};
+// Arguments of one attention launch, in the kernels' parameter order
+// (attn_fwd_kernel takes the first twenty). Pointers are untyped here; the
+// launch casts them to the element type.
+struct AttnArgs {
+    const void *q, *k, *v;
+    void* out;
+    int S, Sk;
+    float scale;
+    int H;
+    long q_bs, q_hs;
+    int q_ss;
+    long k_bs, k_hs;
+    int k_ss;
+    long v_bs, v_hs;
+    int v_ss;
+    long o_bs, o_hs;
+    int o_ss, xcd_grid;
+    void* out2;
+    int s_split;
+    long o2_bs, o2_hs;
+    int o2_ss;
+    const unsigned long long* mask_words;
+    const int *mask_live, *mask_nlive;
+};
+
+template <int D, bool MASKED>
+static void launch_attn_v4(at::ScalarType st, dim3 grid, const AttnArgs& a) {
+    PA_WITH_ELEM16(st, hipLaunchKernelGGL(
+        HIP_KERNEL_NAME(attn_fwd_v4_kernel<D, E, MASKED>), grid, dim3(512), 0,
+        cur_stream(), (const E*)a.q, (const E*)a.k, (const E*)a.v, (E*)a.out,
+        a.S, a.Sk, a.scale, a.H, a.q_bs, a.q_hs, a.q_ss, a.k_bs, a.k_hs,
+        a.k_ss, a.v_bs, a.v_hs, a.v_ss, a.o_bs, a.o_hs, a.o_ss, a.xcd_grid,
+        (E*)a.out2, a.s_split, a.o2_bs, a.o2_hs, a.o2_ss, a.mask_words,
+        a.mask_live, a.mask_nlive));
 }
 
-static std::vector<at::Tensor> attn_fwd_launch_split(
-    at::Tensor q, at::Tensor k, at::Tensor v, double scale, bool bshd,
-    long split, const AttnKeyMask* km = nullptr);
-
-static at::Tensor attn_fwd_launch(at::Tensor q, at::Tensor k, at::Tensor v,
-                                  double scale, bool bshd,
-                                  const AttnKeyMask* km = nullptr) {
-    return attn_fwd_launch_split(q, k, v, scale, bshd, -1, km)[0];
+// PA_ATTN_V3=1: the previous-generation bf16 debug kernel.
+template <int D>
+static void launch_attn_v3(dim3 grid, const AttnArgs& a) {
+    hipLaunchKernelGGL(
+        attn_fwd_kernel<D>, grid, dim3(512), 0, cur_stream(),
+        (const bf16*)a.q, (const bf16*)a.k, (const bf16*)a.v, (bf16*)a.out,
+        a.S, a.Sk, a.scale, a.H, a.q_bs, a.q_hs, a.q_ss, a.k_bs, a.k_hs,
+        a.k_ss, a.v_bs, a.v_hs, a.v_ss, a.o_bs, a.o_hs, a.o_ss);
 }
 
-
-static std::vector<at::Tensor> attn_fwd_launch_split(
+// The one attention launcher. split > 0 (bshd only) writes rows >= split to
+// a second tensor; km != nullptr selects the MASKED instantiations.
+static std::vector<at::Tensor> attn_fwd_launch(
     at::Tensor q, at::Tensor k, at::Tensor v, double scale, bool bshd,
     long split, const AttnKeyMask* km) {
     CHECK_GPU(q);
@@ -2260,32 +2234,11 @@ static std::vector<at::Tensor> attn_fwd_launch_split(
         ? at::empty({B, do_split ? (int)split : S, H, D}, qc.options())
         : at::empty({B, H, S, D}, qc.options());
     at::Tensor out2;
-    void* o2p = nullptr;
-    long o2_bs = 0, o2_hs = 0, ssplit = S;
-    int o2_ss = 0;
-    if (do_split) {
-        out2 = at::empty({B, S - (int)split, H, D}, qc.options());
-        o2p = out2.data_ptr();
-        o2_bs = out2.stride(0);
-        o2_hs = out2.stride(2);
-        o2_ss = (int)out2.stride(1);
-        ssplit = split;
-    }
+    if (do_split) out2 = at::empty({B, S - (int)split, H, D}, qc.options());
     static const bool use_v3 = []() {
         const char* e = getenv("PA_ATTN_V3");
         return e && e[0] == '1';
     }();
-    int xcd_grid = 0;
-    dim3 grid_v4((unsigned)((S + 255) / 256), (unsigned)((long)B * H));
-    dim3 grid((unsigned)((S + 255) / 256), (unsigned)((long)B * H));
-#define PA_ATTN_ARGS_T(T)                                                     \
-    (const T*)qc.data_ptr(), (const T*)kc.data_ptr(),                         \
-    (const T*)vc.data_ptr(), (T*)out.data_ptr(), S, Sk, (float)scale, H,      \
-    qc.stride(b_ax), qc.stride(h_ax), (int)qc.stride(s_ax),                   \
-    kc.stride(b_ax), kc.stride(h_ax), (int)kc.stride(s_ax),                   \
-    vc.stride(b_ax), vc.stride(h_ax), (int)vc.stride(s_ax),                   \
-    out.stride(b_ax), out.stride(h_ax), (int)out.stride(s_ax)
-#define PA_ATTN_ARGS PA_ATTN_ARGS_T(bf16)
     // the previous-generation debug kernel has no fp16 instantiation; its
     // bf16 conversions must never see fp16 bits
     TORCH_CHECK(!use_v3 || qc.scalar_type() == at::kBFloat16,
@@ -2294,86 +2247,75 @@ static std::vector<at::Tensor> attn_fwd_launch_split(
     TORCH_CHECK(!use_v3 || km == nullptr,
                 "attn_fwd: PA_ATTN_V3=1 selects the debug kernel, which has "
                 "no key mask — unset PA_ATTN_V3 for masked attention");
-    if (!use_v3) {
-        const long BH = (long)B * H;
-        const unsigned nq = (unsigned)((S + 255) / 256);
-        if (BH % 8 == 0) {
-            // 1-D XCD-affine grid: same-(b,h) q-tiles share an XCD's L2
-            grid_v4 = dim3((unsigned)(nq * BH), 1);
-            xcd_grid = 1;
-        }
-#define PA_ATTN_MASK_ARGS                                                      \
-    (const unsigned long long*)km->words.data_ptr(),                          \
-    km->live.data_ptr<int>(), km->nlive.data_ptr<int>()
-        if (km != nullptr && D == 128) {
-            PA_WITH_ELEM16(qc.scalar_type(), hipLaunchKernelGGL(
-                HIP_KERNEL_NAME(attn_fwd_v4_kernel<128, E, true>), grid_v4,
-                dim3(512), 0, cur_stream(), PA_ATTN_ARGS_T(E), xcd_grid,
-                (E*)o2p, ssplit, o2_bs, o2_hs, o2_ss, PA_ATTN_MASK_ARGS));
-        } else if (km != nullptr) {
-            PA_WITH_ELEM16(qc.scalar_type(), hipLaunchKernelGGL(
-                HIP_KERNEL_NAME(attn_fwd_v4_kernel<64, E, true>), grid_v4,
-                dim3(512), 0, cur_stream(), PA_ATTN_ARGS_T(E), xcd_grid,
-                (E*)o2p, ssplit, o2_bs, o2_hs, o2_ss, PA_ATTN_MASK_ARGS));
-        } else if (D == 128) {
-            PA_WITH_ELEM16(qc.scalar_type(), hipLaunchKernelGGL(
-                HIP_KERNEL_NAME(attn_fwd_v4_kernel<128, E>), grid_v4,
-                dim3(512), 0, cur_stream(), PA_ATTN_ARGS_T(E), xcd_grid,
-                (E*)o2p, ssplit, o2_bs, o2_hs, o2_ss));
-        } else {
-            PA_WITH_ELEM16(qc.scalar_type(), hipLaunchKernelGGL(
-                HIP_KERNEL_NAME(attn_fwd_v4_kernel<64, E>), grid_v4,
-                dim3(512), 0, cur_stream(), PA_ATTN_ARGS_T(E), xcd_grid,
-                (E*)o2p, ssplit, o2_bs, o2_hs, o2_ss));
-        }
-    } else if (D == 128) {
-        TORCH_CHECK(!do_split, "split output needs the v4 kernel");
-        hipLaunchKernelGGL(attn_fwd_kernel<128>, grid, dim3(512), 0,
-                           cur_stream(), PA_ATTN_ARGS);
+    TORCH_CHECK(!use_v3 || !do_split, "split output needs the v4 kernel");
+    const long BH = (long)B * H;
+    const unsigned nq = (unsigned)((S + 255) / 256);
+    // 1-D XCD-affine grid (v4 only): same-(b,h) q-tiles share an XCD's L2
+    const bool xcd_grid = !use_v3 && BH % 8 == 0;
+    const dim3 grid = xcd_grid ? dim3((unsigned)(nq * BH), 1)
+                               : dim3(nq, (unsigned)BH);
+    const AttnArgs a{
+        qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
+        S, Sk, (float)scale, H,
+        qc.stride(b_ax), qc.stride(h_ax), (int)qc.stride(s_ax),
+        kc.stride(b_ax), kc.stride(h_ax), (int)kc.stride(s_ax),
+        vc.stride(b_ax), vc.stride(h_ax), (int)vc.stride(s_ax),
+        out.stride(b_ax), out.stride(h_ax), (int)out.stride(s_ax),
+        xcd_grid ? 1 : 0,
+        do_split ? out2.data_ptr() : nullptr, do_split ? (int)split : S,
+        do_split ? out2.stride(0) : 0, do_split ? out2.stride(2) : 0,
+        do_split ? (int)out2.stride(1) : 0,
+        km ? (const unsigned long long*)km->words.data_ptr() : nullptr,
+        km ? km->live.data_ptr<int>() : nullptr,
+        km ? km->nlive.data_ptr<int>() : nullptr};
+    const at::ScalarType st = qc.scalar_type();
+    if (use_v3) {
+        if (D == 128) launch_attn_v3<128>(grid, a);
+        else launch_attn_v3<64>(grid, a);
+    } else if (km != nullptr) {
+        if (D == 128) launch_attn_v4<128, true>(st, grid, a);
+        else launch_attn_v4<64, true>(st, grid, a);
     } else {
-        hipLaunchKernelGGL(attn_fwd_kernel<64>, grid, dim3(512), 0,
-                           cur_stream(), PA_ATTN_ARGS);
+        if (D == 128) launch_attn_v4<128, false>(st, grid, a);
+        else launch_attn_v4<64, false>(st, grid, a);
     }
-#undef PA_ATTN_MASK_ARGS
-#undef PA_ATTN_ARGS
-#undef PA_ATTN_ARGS_T
     if (do_split) return {out, out2};
     return {out};
 }
 
 at::Tensor attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, double scale) {
-    return attn_fwd_launch(q, k, v, scale, /*bshd=*/false);
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/false, -1, nullptr)[0];
 }
 
 at::Tensor attn_fwd_bshd(at::Tensor q, at::Tensor k, at::Tensor v, double scale) {
-    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true);
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, -1, nullptr)[0];
 }
 
 std::vector<at::Tensor> attn_fwd_bshd_split(at::Tensor q, at::Tensor k,
                                             at::Tensor v, double scale,
                                             long split) {
-    return attn_fwd_launch_split(q, k, v, scale, /*bshd=*/true, split);
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, split, nullptr);
 }
 
 at::Tensor attn_fwd_masked(at::Tensor q, at::Tensor k, at::Tensor v,
                            double scale, at::Tensor words, at::Tensor live,
                            at::Tensor nlive) {
     const AttnKeyMask km{words, live, nlive};
-    return attn_fwd_launch(q, k, v, scale, /*bshd=*/false, &km);
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/false, -1, &km)[0];
 }
 
 at::Tensor attn_fwd_bshd_masked(at::Tensor q, at::Tensor k, at::Tensor v,
                                 double scale, at::Tensor words,
                                 at::Tensor live, at::Tensor nlive) {
     const AttnKeyMask km{words, live, nlive};
-    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, &km);
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, -1, &km)[0];
 }
 
 std::vector<at::Tensor> attn_fwd_bshd_split_masked(
     at::Tensor q, at::Tensor k, at::Tensor v, double scale, long split,
     at::Tensor words, at::Tensor live, at::Tensor nlive) {
     const AttnKeyMask km{words, live, nlive};
-    return attn_fwd_launch_split(q, k, v, scale, /*bshd=*/true, split, &km);
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, split, &km);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {

@@ -155,15 +155,12 @@ def test_fp8_linear_amax_jump_uses_snapshot_scale():
     assert rel < 0.10, f"fp8 amax-jump error {rel:.4f}"
 
 
-def test_layer_norm_mod_fp8_fused():
-    """Fused AdaLN+fp8 kernel == layer_norm_mod -> quantize, and maintains
-    the same delayed-scaling state contract as quant_fp8."""
+def _check_layer_norm_mod_fp8_fused(B, S, D):
     from comfyui_parallelanything_amd import ops
 
     if not ops.hip_available("layer_norm_mod_fp8"):
         pytest.skip("no layer_norm_mod_fp8 in extension")
     torch.manual_seed(5)
-    B, S, D = 2, 64, 1024
     x = torch.randn(B, S, D, device="cuda", dtype=torch.bfloat16)
     sc = torch.randn(B, D, device="cuda", dtype=torch.bfloat16) * 0.1
     sh = torch.randn(B, D, device="cuda", dtype=torch.bfloat16) * 0.1
@@ -182,6 +179,75 @@ def test_layer_norm_mod_fp8_fused():
     assert abs(amax[0].item() - true_amax * 0.999) < 2e-2
     assert amax[1].item() == 0.0
     assert used.item() == qscale.new_tensor([s0]).item()
+
+
+def test_layer_norm_mod_fp8_fused():
+    """Fused AdaLN+fp8 kernel == layer_norm_mod -> quantize, and maintains
+    the same delayed-scaling state contract as quant_fp8."""
+    _check_layer_norm_mod_fp8_fused(2, 64, 1024)
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 8), (2, 3, 8 * 257)])
+def test_layer_norm_mod_fp8_fused_block_edges(shape):
+    """Same check where the block-level amax reduce is thinnest: one active
+    thread per 256-thread block (D=8), and a row of 257 vectors, where
+    thread 0 alone makes a second pass."""
+    _check_layer_norm_mod_fp8_fused(*shape)
+
+
+# single nonzero element: (numel, flat position)
+_AMAX_SPOTS = {
+    "first": (8 * 256, 0),
+    # last element of vector 255 = last lane of the last wave of block 0
+    "block0_last_lane": (8 * 256, 8 * 256 - 1),
+    # 4096 blocks x 256 threads x 2 vectors + 5: the smallest size at which
+    # the grid-stride loop's second and (partial) third ILP slots run; below
+    # 4096*256 vectors every thread sees at most one vector
+    "third_ilp_slot": (8 * (4096 * 256 * 2 + 5), 8 * (4096 * 256 * 2 + 5) - 1),
+}
+
+
+@pytest.mark.parametrize("spot", sorted(_AMAX_SPOTS))
+@pytest.mark.parametrize("op,value,amax_tol", [("quant_fp8", -3.0, 1e-3),
+                                               ("gelu_fp8", 3.0, 2e-2)])
+def test_fp8_amax_single_nonzero_element(op, value, amax_tol, spot):
+    """One nonzero element in a zero tensor must reach amax_buf[0] from
+    wherever it sits (the wave shuffle, the per-wave scratch and the
+    conditional atomicMax each see exactly one contributor), and must be
+    the only nonzero output."""
+    from comfyui_parallelanything_amd import ops
+
+    if not ops.hip_available(op):
+        pytest.skip(f"no {op} in extension")
+    numel, pos = _AMAX_SPOTS[spot]
+    x = torch.zeros(numel, device="cuda", dtype=torch.bfloat16)
+    x[pos] = value
+    want = torch.tensor(value)
+    if op == "gelu_fp8":
+        want = torch.nn.functional.gelu(want, approximate="tanh")
+    want = want.item()
+    s0 = 2.0 ** -7  # 3.0 / s0 = 384 is an e4m3 value below the 448 clamp
+    scale = torch.tensor([s0], device="cuda")
+    amax = torch.zeros(2, device="cuda")
+    used = torch.zeros(1, device="cuda")
+    if op == "quant_fp8":
+        x8 = ops.quant_fp8(x, scale, amax, scale_used=used)
+    else:
+        x8 = ops.gelu_fp8(x, scale, amax, used)
+    # state contract: decayed amax, retired counter slot, next scale, snapshot
+    assert abs(amax[0].item() - abs(want) * 0.999) < amax_tol
+    assert amax[1].item() == 0.0
+    assert abs(scale.item() - max(amax[0].item() / 448.0, 1e-12)) < 1e-6
+    assert used.item() == s0, "scale_used must be the entry scale bits"
+    # output: that value at that position (within one fp8 ULP of the
+    # reference cast, as in test_quant_fp8_fused_scale_epilogue), zero elsewhere
+    q = x8.float()
+    assert torch.count_nonzero(q).item() == 1
+    ref = torch.tensor(want / s0).clamp(-448, 448).to(
+        torch.float8_e4m3fn).float().item()
+    ulp = max(abs(ref) * 2 ** -3, 2 ** -9)
+    assert abs(q[pos].item() - ref) <= ulp
+    assert abs(q[pos].item() * used.item() - want) <= ulp * s0
 
 
 def test_fp8_linear_forward_ln_matches_composed():
