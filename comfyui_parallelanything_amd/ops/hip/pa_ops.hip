@@ -1504,13 +1504,35 @@ __global__ void pack_joint_qkv_kernel(
     }
 }
 
+// Half-wave exchange without LDS: combine x with the partner lane's x
+// (lane i <-> lane i^32). v_permlane32_swap trades the upper half of its
+// first operand for the lower half of its second, so of the two results one
+// is this lane's own x and the other its partner's; which is which depends
+// on the half, and a commutative f gives both lanes the same bits. A VALU
+// op: no ds_bpermute round trip and no lgkmcnt wait in the caller's chain.
+template <typename F>
+PA_DEV float half_swap_combine(float x, F f) {
+    const unsigned int u = __float_as_uint(x);
+    auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return f(__uint_as_float((unsigned int)r[0]),
+             __uint_as_float((unsigned int)r[1]));
+}
+// One v_mul_f32 that the SLP vectorizer cannot pair into v_pk_mul_f32
+// (packed f32 VALU beside MFMAs costs more than the two scalar ops).
+PA_DEV float mul_f32_scalar(float a, float b) {
+    float r;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
 // ---------------------------------------------------------------------------
 // Attention v4: swapped-QK^T 32x32 structure (guide Appendix B ladder).
 //
 // mfma_f32_32x32x16_bf16 computing S^T = K·Q^T, so each LANE owns a full
-// query ROW: softmax max/sum are a 32-value local reduce + ONE
-// __shfl_xor(32) with the partner lane; running (m, l) and the per-tile
-// O-rescale are lane-local scalars. P converts f32->bf16 in-register
+// query ROW: softmax max/sum are a 32-value local reduce + ONE half-wave
+// exchange with the partner lane (half_swap_combine, no LDS); running (m, l)
+// and the per-tile O-rescale are lane-local scalars. P converts f32->bf16
+// in-register
 // (v_cvt_pk_bf16_f32) and redistributes across half-waves with
 // v_permlane32_swap (T12) — NO P staging through LDS. PV computes
 // O^T = V^T · P^T (same P fragments serve as the B operand), keeping the
@@ -1705,30 +1727,51 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
         // value (kt, reg) = S[row][key = kt*32 + (reg&3) + 8*(reg>>2) + 4*hi]
         // raw tile max (scale2 > 0 commutes with max), softmax scale fused
         // into the exp2 argument as one FMA per element.
-        float mx = -3e30f;
-        // MASKED: this lane's keys are bits 4*hi + (r&3) + 8*(r>>2) of the
-        // word's half kt — one 64-bit shift, then constant bit positions
-        unsigned int wh[2] = {0u, 0u};
-        if constexpr (MASKED) {
-            const unsigned long long wl = word >> (4 * hi);
-            wh[0] = (unsigned int)wl;
-            wh[1] = (unsigned int)(wl >> 32);
+        //
+        // Per-key validity only where a tile can hold a dead key: `full` is
+        // block-uniform (Sk and kv0 are scalars, the mask word is pinned in
+        // SGPRs), so a full tile branches over the whole substitution — no
+        // key index, compare or select — and uses the scores as qk_phase
+        // left them. Every tile of an Sk % 64 == 0 call is full. The
+        // substitution works in place ahead of ONE softmax body: a second,
+        // compile-time-full copy of the body costs registers (D=128 spills,
+        // D=64 loses a resident block; scripts/attn_v6.hip v4/v5).
+        bool full;
+        if constexpr (MASKED) full = word == ~0ull;
+        else full = kv0 + KVBLK <= Sk;
+        if (!full) {
+            // MASKED: this lane's keys are bits 4*hi + (r&3) + 8*(r>>2) of
+            // the word's half kt — one 64-bit shift, then constant bit
+            // positions
+            unsigned int wh[2] = {0u, 0u};
+            if constexpr (MASKED) {
+                const unsigned long long wl = word >> (4 * hi);
+                wh[0] = (unsigned int)wl;
+                wh[1] = (unsigned int)(wl >> 32);
+            }
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key =
+                        kv0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    bool valid;
+                    if constexpr (MASKED)
+                        valid =
+                            ((wh[kt] >> ((r & 3) + 8 * (r >> 2))) & 1u) != 0;
+                    else
+                        valid = key < Sk;
+                    st[kt][r] = valid ? st[kt][r] : -3e30f;
+                }
         }
+        float mx = -3e30f;
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = kv0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                bool valid;
-                if constexpr (MASKED)
-                    valid = ((wh[kt] >> ((r & 3) + 8 * (r >> 2))) & 1u) != 0;
-                else
-                    valid = key < Sk;
-                const float sv = valid ? st[kt][r] : -3e30f;
-                st[kt][r] = sv;
-                mx = fmaxf(mx, sv);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // partner: row's other 32 keys
+            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[kt][r]);
+        // partner: row's other 32 keys
+        mx = half_swap_combine(
+            mx, [](float a, float c) { return fmaxf(a, c); });
         const float mnew = fmaxf(m_run, mx * scale2);
         const float alpha = __builtin_amdgcn_exp2f(m_run - mnew);
         m_run = mnew;
@@ -1742,13 +1785,22 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
                 st[kt][r] = pv_;
                 ps += pv_;
             }
-        ps += __shfl_xor(ps, 32, 64);
+        ps = half_swap_combine(ps, [](float a, float c) { return a + c; });
         l_run = l_run * alpha + ps;
         if (alpha != 1.f) {
+            // D=128: 64 scalar v_mul_f32; left to the compiler they become
+            // 32 v_pk_mul_f32, slower beside the MFMAs there. D=64 measured
+            // the other way round and keeps the packed form
+            // (scripts/attn_v6.hip, v3 against v2).
 #pragma unroll
             for (int n = 0; n < NV; ++n)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) o_acc[n][r] *= alpha;
+                for (int r = 0; r < 16; ++r) {
+                    if constexpr (D == 128)
+                        o_acc[n][r] = mul_f32_scalar(o_acc[n][r], alpha);
+                    else
+                        o_acc[n][r] *= alpha;
+                }
         }
         // P f32 -> 16-bit fragments via cvt_pk + permlane32_swap: chunk c
         // (16 keys) uses regs 8*(c&1)..+7 of st[c>>1]; after the half-swap
