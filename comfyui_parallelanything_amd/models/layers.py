@@ -446,19 +446,23 @@ class ModulationBank:
             # quantized/wrapped projections: banking disabled, blocks
             # compute their own modulation (mods=None path)
             raise TypeError("ModulationBank requires plain nn.Linear mods")
-        self.weight = None
-        self.bias = None
+        # (weight, bias), published as ONE attribute: micro-batch threads
+        # share the lead replica, and a second thread must never see the
+        # weight of a build in progress without its bias
+        self._wb = None
         self.splits = [m.lin.out_features for m in self.mods]
 
     def _build(self):
-        self.weight = torch.cat([m.lin.weight for m in self.mods], dim=0)
-        self.bias = torch.cat([m.lin.bias for m in self.mods], dim=0)
+        self._wb = (torch.cat([m.lin.weight for m in self.mods], dim=0),
+                    torch.cat([m.lin.bias for m in self.mods], dim=0))
+        return self._wb
 
     def __call__(self, vec):
-        if self.weight is None or self.weight.device != vec.device:
-            self._build()
+        wb = self._wb
+        if wb is None or wb[0].device != vec.device:
+            wb = self._build()
         out = torch.nn.functional.linear(
-            torch.nn.functional.silu(vec), self.weight, self.bias
+            torch.nn.functional.silu(vec), wb[0], wb[1]
         )
         results = []
         off = 0

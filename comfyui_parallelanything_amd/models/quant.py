@@ -53,8 +53,9 @@ class FP8Linear(nn.Module):
         self.in_features = weight_fp8.shape[1]
         self.out_features = weight_fp8.shape[0]
         # delayed activation scaling: running amax + next-call scale are
-        # maintained ENTIRELY by the quant kernel (slot 1 of a_amax is its
-        # block counter; see pa_ops.hip quant_fp8 fused epilogue) — zero
+        # maintained ENTIRELY on the device (the quant kernel and the
+        # finalize kernel launched right after it, see ops/hip/fp8.h; slot 1
+        # of a_amax is a retired block counter and stays zero) — zero
         # per-call host-launched scale math. The scale used is the
         # PREVIOUS call's. Buffers MUST live on the weight's device — the
         # module is swapped in place and never .to()-ed afterwards.

@@ -312,10 +312,7 @@ def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None,
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     km = None if key_mask is None else _key_mask_for(key_mask, q)
-    # the v3 debug kernel has no split-output epilogue: under PA_ATTN_V3 the
-    # op composes from the plain kernel + slices, so the escape hatch covers
-    # the whole op surface
-    if q.is_cuda and os.environ.get("PA_ATTN_V3") != "1":
+    if q.is_cuda:
         out, why = _attn_native(q, k, v, scale, km, bshd=True, split=split)
         if out is not None:
             a, b = out

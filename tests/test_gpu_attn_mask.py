@@ -350,26 +350,39 @@ def test_launcher_rejects_mismatched_masks():
         ops.attention_bshd(q, k, k, key_mask=torch.stack([all_true(100)] * 3))
 
 
-def test_v3_debug_kernel_rejects_masks():
-    """PA_ATTN_V3=1 selects the previous-generation kernel, which has no
-    mask: it must raise, as it does for fp16 (the env var is read once per
-    process, hence the child)."""
+def test_retired_v3_env_never_gives_a_wrong_result():
+    """PA_ATTN_V3=1 once selected a bf16-only kernel without masks, which
+    had to refuse fp16 and masked calls. The kernel and the option are
+    retired: with the variable set, an fp16 call, a masked call and a masked
+    split call (last 20 of 64 keys dead) match the fp32 reference at this
+    file's tolerance. Child process: the variable was read once per
+    process."""
     code = (
         "import torch\n"
         "from comfyui_parallelanything_amd import ops\n"
-        "q = torch.randn(1, 64, 2, 64, device='cuda', dtype=torch.bfloat16)\n"
-        "m = torch.ones(1, 64, dtype=torch.bool, device='cuda')\n"
-        "for call in (lambda: ops.attention_bshd(q, q, q, key_mask=m),\n"
-        "             lambda: ops.attention_bshd_split(q, q, q, 16,"
-        " key_mask=m)):\n"
-        "    try:\n"
-        "        call()\n"
-        "    except RuntimeError as e:\n"
-        "        assert 'no key mask' in str(e), e\n"
-        "    else:\n"
-        "        raise SystemExit('masked call ran on the v3 debug kernel')\n"
-        "ops.attention_bshd(q, q, q)\n"
-        "torch.cuda.synchronize()\n"
+        "from comfyui_parallelanything_amd.ops import reference as R\n"
+        "torch.manual_seed(31)\n"
+        "def ref(q, k, v, m=None):\n"
+        "    p = lambda t: t.permute(0, 2, 1, 3).float()\n"
+        "    return R.attention(p(q), p(k), p(v), None,"
+        " key_mask=m).permute(0, 2, 1, 3)\n"
+        "def close(out, want, dtype):\n"
+        "    assert out.dtype == dtype, out.dtype\n"
+        f"    torch.testing.assert_close(out.float(), want,"
+        f" rtol={RTOL}, atol={ATOL})\n"
+        "h = [torch.randn(1, 64, 2, 64, device='cuda', dtype=torch.float16)\n"
+        "     for _ in range(3)]\n"
+        "close(ops.attention_bshd(*h), ref(*h), torch.float16)\n"
+        "b = [torch.randn(1, 64, 2, 64, device='cuda', dtype=torch.bfloat16)\n"
+        "     for _ in range(3)]\n"
+        "m = (torch.arange(64, device='cuda') < 44)[None]\n"
+        "want = ref(*b, m)\n"
+        "assert (want - ref(*b)).abs().max() > 1e-2, 'mask masks nothing'\n"
+        "close(ops.attention_bshd(*b, key_mask=m), want, torch.bfloat16)\n"
+        "lo, hi = ops.attention_bshd_split(*b, 16, key_mask=m)\n"
+        "assert lo.shape[1] == 16 and hi.shape[1] == 48\n"
+        "close(torch.cat([lo, hi], dim=1), want, torch.bfloat16)\n"
+        "assert not ops._WARNED, ops._WARNED\n"
     )
     env = dict(os.environ, PA_ATTN_V3="1")
     r = subprocess.run([sys.executable, "-c", code], env=env,

@@ -15,10 +15,7 @@ tolerances of the matching bf16 tests. On top of that:
 Run on an MI355X box:  python -m pytest tests/test_gpu_fp16.py -m gpu -q
 """
 import copy
-import os
 import re
-import subprocess
-import sys
 
 import pytest
 import torch
@@ -373,30 +370,6 @@ def test_qk_norm_rope_mixed_weight_dtype_raises():
     with pytest.raises(RuntimeError, match="must match"):
         ops.qk_norm_rope_(q, k, w16, wb, cs)
     assert torch.equal(q, before), "q was modified by a rejected call"
-
-
-# ---------------- PA_ATTN_V3=1 stays bf16-only ----------------
-
-def test_attn_v3_debug_kernel_rejects_fp16():
-    """The previous-generation kernel must refuse fp16, never reinterpret
-    its bits as bf16. Fresh process: the env var is read once per process."""
-    code = (
-        "import sys, torch;"
-        "from comfyui_parallelanything_amd import ops;"
-        "q=torch.randn(1,2,128,128,device='cuda',dtype=torch.float16);"
-        "k=torch.randn_like(q); v=torch.randn_like(q);\n"
-        "try:\n"
-        "    ops.attention(q,k,v)\n"
-        "except RuntimeError as e:\n"
-        "    sys.exit(0 if 'bf16-only debug kernel' in str(e) else 3)\n"
-        "sys.exit(2)\n"
-    )
-    env = dict(os.environ, PA_ATTN_V3="1")
-    r = subprocess.run([sys.executable, "-c", code], env=env,
-                       cwd=os.path.dirname(os.path.dirname(__file__)))
-    assert r.returncode == 0, (
-        f"exit {r.returncode}: 2 = no error raised, 3 = wrong message"
-    )
 
 
 # ---------------- whole-model composition ----------------

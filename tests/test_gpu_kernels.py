@@ -280,7 +280,8 @@ def test_gelu_tanh_strided_slice():
 
 
 def test_attn_v3_fallback_env():
-    """PA_ATTN_V3=1 selects the previous-generation kernel; numerics hold."""
+    """PA_ATTN_V3=1 once selected the previous-generation kernel. The kernel
+    and the option are retired; with the variable set, numerics hold."""
     import os
     import subprocess
     import sys
@@ -381,3 +382,128 @@ def test_whole_model_gpu_vs_cpu_reference(name):
     assert rel < 0.15, f"{name}: whole-model rel-l2 {rel:.4f}"
     corr = torch.corrcoef(torch.stack([out.flatten(), ref.flatten()]))[0, 1]
     assert corr > 0.99, f"{name}: correlation {corr:.4f}"
+
+
+# ---------------- small shapes: tails, scalar rungs, gelu exits ----------------
+
+DT16 = pytest.mark.parametrize(
+    "dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+
+
+def _qk_ref(qkv_part, w, cs):
+    """[B,S,H,D] view -> fp32 rms_norm + rope, back in [B,S,H,D]."""
+    x = qkv_part.permute(0, 2, 1, 3).float()
+    return R.rope_apply(R.rms_norm(x, w.float()), cs).permute(0, 2, 1, 3)
+
+
+@DT16
+@pytest.mark.parametrize("D", [40, 64, 128])
+@pytest.mark.parametrize("B,S,H", [(1, 3, 3), (1, 2, 3), (1, 1, 3)])
+def test_qk_norm_rope_row_tails(B, S, H, D, dtype):
+    """9, 6 and 3 rows: every residue of the 4-rows-per-wave tail. D=40
+    leaves 44 idle lanes that still feed the 64-lane reduction. The v third
+    of the fused buffer is not touched."""
+    torch.manual_seed(13)
+    qkv = torch.randn(B, S, 3, H, D, device="cuda", dtype=dtype)
+    before = qkv.clone()
+    q, k, v = qkv.unbind(2)
+    wq = torch.randn(D, device="cuda", dtype=dtype)
+    wk = torch.randn(D, device="cuda", dtype=dtype)
+    cs = R.rope_freqs(torch.arange(S, device="cuda"), D)
+    ops.qk_norm_rope_(q, k, wq, wk, cs)
+    _cmp(q, _qk_ref(before[:, :, 0], wq, cs), 3e-2, 3e-2, "q")
+    _cmp(k, _qk_ref(before[:, :, 1], wk, cs), 3e-2, 3e-2, "k")
+    assert torch.equal(qkv[:, :, 2], before[:, :, 2]), "v was modified"
+
+
+@DT16
+@pytest.mark.parametrize("D", [40, 128])
+@pytest.mark.parametrize("B,T,Si,H", [(1, 2, 3, 3), (1, 1, 1, 1)])
+def test_pack_joint_qkv_row_tails(B, T, Si, H, D, dtype):
+    torch.manual_seed(14)
+    txt = torch.randn(B, T, 3, H, D, device="cuda", dtype=dtype)
+    img = torch.randn(B, Si, 3, H, D, device="cuda", dtype=dtype)
+    wq_t, wk_t, wq_i, wk_i = (
+        torch.randn(D, device="cuda", dtype=dtype) for _ in range(4))
+    cs = R.rope_freqs(torch.arange(T + Si, device="cuda"), D)
+    q, k, v = ops.pack_joint_qkv(txt, img, wq_t, wk_t, wq_i, wk_i, cs)
+    ref_q = torch.cat([_qk_ref(txt[:, :, 0], wq_t, cs[:T]),
+                       _qk_ref(img[:, :, 0], wq_i, cs[T:])], dim=1)
+    ref_k = torch.cat([_qk_ref(txt[:, :, 1], wk_t, cs[:T]),
+                       _qk_ref(img[:, :, 1], wk_i, cs[T:])], dim=1)
+    _cmp(q, ref_q, 3e-2, 3e-2, "pack q")
+    _cmp(k, ref_k, 3e-2, 3e-2, "pack k")
+    assert torch.equal(v, torch.cat([txt[:, :, 2], img[:, :, 2]], dim=1)), \
+        "v is not a bitwise passthrough"
+
+
+@DT16
+def test_scalar_rungs_16bit_unaligned_d(dtype):
+    """D=20 is no multiple of 8: the 16-bit scalar kernels, not the vector
+    ones. Tolerances of the vector-path tests above."""
+    torch.manual_seed(15)
+    B, S, D = 2, 5, 20
+    x = torch.randn(B, S, D, device="cuda", dtype=dtype)
+    w = torch.randn(D, device="cuda", dtype=dtype)
+    sc = torch.randn(B, D, device="cuda", dtype=dtype)
+    sh = torch.randn(B, D, device="cuda", dtype=dtype)
+    r = torch.randn(B, S, D, device="cuda", dtype=dtype)
+    _cmp(ops.rms_norm(x, w), R.rms_norm(x.float(), w.float()),
+         2e-2, 2e-2, "rms_norm")
+    _cmp(ops.layer_norm_mod(x, sc, sh),
+         R.layer_norm_mod(x.float(), sc.float(), sh.float()),
+         2e-2, 5e-2, "layer_norm_mod")
+    _cmp(ops.gate_residual(r, sc, x),
+         R.gate_residual(r.float(), sc.float(), x.float()),
+         2e-2, 2e-2, "gate_residual")
+
+
+def test_scalar_rungs_fp32():
+    """fp32 inputs take the scalar kernels; test_rms_norm_fp32's tolerance."""
+    torch.manual_seed(16)
+    B, S, D = 2, 5, 24
+    x = torch.randn(B, S, D, device="cuda")
+    sc = torch.randn(B, D, device="cuda")
+    sh = torch.randn(B, D, device="cuda")
+    r = torch.randn(B, S, D, device="cuda")
+    for out in (ops.layer_norm_mod(x, sc, sh), ops.gate_residual(r, sc, x)):
+        assert out.dtype == torch.float32
+    _cmp(ops.layer_norm_mod(x, sc, sh), R.layer_norm_mod(x, sc, sh),
+         1e-5, 1e-5, "layer_norm_mod fp32")
+    _cmp(ops.gate_residual(r, sc, x), R.gate_residual(r, sc, x),
+         1e-5, 1e-5, "gate_residual fp32")
+    xr = torch.randn(1, 2, 5, 8, device="cuda")
+    cs = R.rope_freqs(torch.arange(5, device="cuda"), 8)
+    _cmp(ops.rope_apply(xr, cs), R.rope_apply(xr, cs), 1e-5, 1e-5,
+         "rope_apply fp32")
+    xg = torch.randn(1, 8, 3, 3, device="cuda")
+    wg = torch.randn(8, device="cuda")
+    bg = torch.randn(8, device="cuda")
+    _cmp(ops.group_norm_silu(xg, 4, wg, bg), R.group_norm_silu(xg, 4, wg, bg),
+         1e-5, 1e-5, "group_norm_silu fp32")
+
+
+def test_rms_norm_rejects_float64():
+    x = torch.randn(2, 16, device="cuda", dtype=torch.float64)
+    with pytest.raises(RuntimeError, match="unsupported dtype"):
+        ops.rms_norm(x, None)
+
+
+@DT16
+@pytest.mark.parametrize(
+    "make",
+    [
+        lambda dt: torch.randn(24, 16, device="cuda", dtype=dt).t(),  # copy
+        lambda dt: torch.randn(4, 6, device="cuda", dtype=dt),   # w % 8 != 0
+        lambda dt: torch.randn(3, 5, device="cuda", dtype=dt),   # at::gelu
+        lambda dt: torch.randn(16, device="cuda", dtype=dt),     # 1-D
+    ],
+    ids=["transposed", "w6", "numel15", "1d"],
+)
+def test_gelu_tanh_exits(make, dtype):
+    torch.manual_seed(17)
+    x = make(dtype)
+    out = ops.gelu_tanh(x)
+    assert out.shape == x.shape and out.dtype == dtype
+    ref = torch.nn.functional.gelu(x.float(), approximate="tanh")
+    _cmp(out, ref, 2e-2, 2e-2, "gelu exits")
