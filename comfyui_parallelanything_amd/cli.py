@@ -52,10 +52,18 @@ def main(argv=None):
                     help="real prompt length(s): one value for the whole "
                          "batch or one per sample; the rest of the context "
                          "is padding, passed to the model as attention_mask")
+    ap.add_argument("--frame-window", type=int, default=None, metavar="N",
+                    help="wan models: block-sparse self-attention over "
+                         "frames within N of the query's (default: dense)")
     ap.add_argument("--json-out", default=None,
                     help="write the run summary as one JSON record")
     args = ap.parse_args(argv)
 
+    if args.frame_window is not None:
+        if not args.model.startswith("wan"):
+            ap.error("--frame-window applies to wan models only")
+        if args.frame_window < 0:
+            ap.error("--frame-window must be >= 0")
     devices = args.devices.split(",")
     pcts = (
         [float(p) for p in args.percent.split(",")]
@@ -79,6 +87,8 @@ def main(argv=None):
     )
     make, make_inputs = MODELS[args.model]
     model = make(dev=chain.lead, dtype=dtype, tiny=tiny)
+    if args.frame_window is not None:
+        model.cfg.self_attn_frame_window = args.frame_window
 
     if args.lora:
         from .models.lora import merge_lora_file
@@ -129,6 +139,7 @@ def main(argv=None):
         "devices": devices, "percent": pcts,
         "dtype": str(dtype).replace("torch.", ""), "tiny": tiny,
         "engine": "in-process", "text_len": text_len,
+        "frame_window": args.frame_window,
     }
     print(json.dumps(summary, indent=2))
     if args.json_out:

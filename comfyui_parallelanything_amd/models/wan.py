@@ -55,10 +55,12 @@ class WanBlock(nn.Module):
         self.cross_proj = nn.Linear(dim, dim)
         self.ffn = FusedMLP(dim, ffn_dim, dim)
 
-    def forward(self, x, e, context, pe, key_mask=None):
+    def forward(self, x, e, context, pe, key_mask=None, block_mask=None):
         # e: [B, 6, dim] time-modulation; learned bias added per block
         # key_mask: optional ops.KeyMask over the context tokens — masks the
-        # cross-attention only; the space-time self-attention stays unmasked
+        # cross-attention only
+        # block_mask: optional ops.BlockMask over the space-time tokens —
+        # sparsifies the self-attention only (WanConfig.self_attn_frame_window)
         m = (e + self.mod).unbind(dim=1)  # 6 x [B, dim]
         shift1, scale1, gate1, shift2, scale2, gate2 = m
 
@@ -70,7 +72,8 @@ class WanBlock(nn.Module):
             q, k, self.self_norm.query_norm.scale,
             self.self_norm.key_norm.scale, pe,
         )
-        attn = ops.attention_bshd(q, k, v, self.scale).flatten(2)
+        attn = ops.attention_bshd(q, k, v, self.scale,
+                                  block_mask=block_mask).flatten(2)
         x = ops.gate_residual(x, gate1, self.self_proj(attn))
 
         h = self.norm_cross(x)
@@ -105,6 +108,11 @@ class WanConfig:
     axes_dim: Tuple[int, ...] = (44, 42, 42)
     theta: float = 10000.0
     time_embed_dim: int = 256
+    # Block-sparse self-attention: every 256-token query block attends the
+    # 64-token key tiles that touch a frame within this many frames of one
+    # of its own (ops.frame_window_block_mask). None, or a window that
+    # reaches every frame (>= frames - 1), is dense attention.
+    self_attn_frame_window: Optional[int] = None
 
     @classmethod
     def wan22_a14b(cls) -> "WanConfig":
@@ -154,6 +162,29 @@ class WanDiT(nn.Module):
         self.head_mod = nn.Linear(cfg.dim, cfg.dim * 2)
         self.head = nn.Linear(cfg.dim, self.patch_dim)
         self._pe_cache: dict = {}
+        self._mask_cache: dict = {}  # packed frame-window BlockMasks
+
+    def _frame_window_mask(self, B, f, tokens_per_frame, device):
+        """The packed self-attention BlockMask, or None for dense attention.
+        Packed once per (batch, grid, window, device): a replica behind the
+        engine's batch split sees its own chunk's batch size."""
+        window = self.cfg.self_attn_frame_window
+        if window is None:
+            return None
+        if window < 0:
+            raise ValueError(f"self_attn_frame_window must be >= 0, got "
+                             f"{window}")
+        if window >= f - 1:
+            return None
+        key = (B, f, tokens_per_frame, window, str(device))
+        bm = self._mask_cache.get(key)
+        if bm is None:
+            S = f * tokens_per_frame
+            bm = ops.pack_block_mask(
+                ops.frame_window_block_mask(f, tokens_per_frame, window,
+                                            device=device), B, S, S)
+            self._mask_cache[key] = bm
+        return bm
 
     def _pe(self, f, h, w, device):
         key = (f, h, w, str(device))
@@ -204,6 +235,9 @@ class WanDiT(nn.Module):
         if attention_mask is not None:
             # packed once per forward, shared by every block's cross-attention
             mk["key_mask"] = context_key_mask(attention_mask, ctx)
+        bm = self._frame_window_mask(B, f, h * w, x.device)
+        if bm is not None:
+            mk["block_mask"] = bm
         for block in self.transformer_blocks:
             seq = block(seq, e, ctx, pe, **mk)
         shift, scale = self.head_mod(torch.nn.functional.silu(tvec)).chunk(2, dim=-1)

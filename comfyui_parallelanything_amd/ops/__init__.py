@@ -213,15 +213,165 @@ def _key_mask_for(key_mask, q) -> KeyMask:
     return km
 
 
-def _attn_native(q, k, v, scale: float, km: Optional[KeyMask], bshd: bool,
+# Block-mask granularity: the attention kernel's own geometry.
+ATTN_Q_BLOCK = reference.Q_BLOCK    # 256 query rows per block
+ATTN_KV_TILE = reference.KV_TILE    # 64 keys per tile
+
+
+@dataclass
+class BlockMask:
+    """A [nq, nk] block mask packed for the block-list attention kernels,
+    nq = ceil(Sq/256), nk = ceil(Sk/64), optionally composed with a [B, Sk]
+    key mask.
+
+    Tensors, plus the three integers the pack was made for (checked before
+    every launch; parallel.pipeline's recursive move carries the tensors
+    across devices and leaves the integers as they are):
+      block  bool [nq, nk], True = the query block attends the key tile
+      keys   optional bool [B, Sk] key mask, True = attend
+      words  [B, nk] int64: pack_key_mask's words for ``keys``, or for an
+             all-true mask without one (bits at or beyond Sk are 0)
+      live   [B, nq, nk] int32: per (b, query block) the ascending tiles t
+             with block[qb][t] and words[b][t] != 0, compacted, zero tail
+      nlive  [B, nq] int32
+    On CPU only ``block`` and ``keys`` are set. ``live`` indexes ``words``
+    and drives the kernel's global loads, so the pack kernel is its only
+    producer: build one with pack_block_mask, never by hand.
+    """
+    block: torch.Tensor
+    keys: Optional[torch.Tensor] = None
+    words: Optional[torch.Tensor] = None
+    live: Optional[torch.Tensor] = None
+    nlive: Optional[torch.Tensor] = None
+    batch: int = 0
+    Sq: int = 0
+    Sk: int = 0
+
+
+def pack_block_mask(block_mask, batch: int, Sq: int, Sk: int,
+                    key_mask=None) -> BlockMask:
+    """Pack a [ceil(Sq/256), ceil(Sk/64)] bool/integer block mask (nonzero =
+    the 256-row query block attends the 64-key tile) once, for any number of
+    attention calls of that batch size and those lengths. The mask is shared
+    by all batch elements and heads.
+
+    Contract of every ``block_mask=`` argument below: key j is visible to
+    query row i of batch element b iff block_mask[i // 256][j // 64] and (no
+    key mask or key_mask[b][j]). A query row with no visible key returns
+    zeros. K/V rows at keys that no query block of that batch element sees
+    are don't-care (any bit pattern, NaN included). Floating masks raise, as
+    in pack_key_mask; another shape raises ValueError. ``key_mask`` is a
+    KeyMask or a raw [batch, Sk] mask and becomes part of the pack.
+    """
+    batch, Sq, Sk = int(batch), int(Sq), int(Sk)
+    bm = reference.as_bool_block_mask(block_mask, Sq, Sk)
+    keys = None
+    if key_mask is not None:
+        keys = (key_mask.mask if isinstance(key_mask, KeyMask)
+                else reference.as_bool_key_mask(key_mask))
+        if tuple(keys.shape) != (batch, Sk):
+            raise ValueError(f"key mask {list(keys.shape)} does not match "
+                             f"[batch={batch}, Sk={Sk}]")
+        if keys.device != bm.device:
+            raise ValueError(f"key mask on {keys.device}, block mask on "
+                             f"{bm.device}")
+    if bm.is_cuda:
+        ext = _require_ext("pack_block_lists")
+        if ext is not None:
+            if isinstance(key_mask, KeyMask) and key_mask.words is not None:
+                words = key_mask.words
+            else:
+                words = pack_key_mask(
+                    keys if keys is not None else
+                    torch.ones(batch, Sk, dtype=torch.bool,
+                               device=bm.device)).words
+            live, nlive = ext.pack_block_lists(bm, words)
+            return BlockMask(bm, keys, words, live, nlive, batch, Sq, Sk)
+    return BlockMask(bm, keys, batch=batch, Sq=Sq, Sk=Sk)
+
+
+def frame_window_block_mask(frames: int, tokens_per_frame: int, window: int,
+                            device=None) -> torch.Tensor:
+    """Block mask [ceil(S/256), ceil(S/64)], S = frames * tokens_per_frame,
+    for video tokens in (frame, row, col) order: a query block attends a key
+    tile iff some frame the tile touches lies within ``window`` frames of
+    some frame the query block touches.
+
+    Query block i spans frames qlo = 256i // T .. qhi = (min(256(i+1), S) -
+    1) // T (T = tokens_per_frame), tile t spans klo .. khi the same way
+    with 64, and the block is live iff khi >= qlo - window and klo <= qhi +
+    window. That is a block-level superset of "attend frames within
+    +-window"; the block mask is the definition."""
+    frames, T, window = int(frames), int(tokens_per_frame), int(window)
+    if frames < 1 or T < 1 or window < 0:
+        raise ValueError(f"frame_window_block_mask: frames={frames}, "
+                         f"tokens_per_frame={T}, window={window}")
+    S = frames * T
+    nq, nk = reference.block_mask_shape(S, S)
+
+    def spans(n, step):
+        lo = torch.arange(n, device=device, dtype=torch.int64) * step
+        hi = torch.clamp(lo + step, max=S) - 1
+        return lo // T, hi // T
+
+    qlo, qhi = spans(nq, ATTN_Q_BLOCK)
+    klo, khi = spans(nk, ATTN_KV_TILE)
+    return ((khi[None, :] >= qlo[:, None] - window)
+            & (klo[None, :] <= qhi[:, None] + window))
+
+
+def _block_mask_for(block_mask, key_mask, q, Sq: int, Sk: int) -> BlockMask:
+    B = q.shape[0]
+    if not isinstance(block_mask, BlockMask):
+        if block_mask.device != q.device:
+            raise ValueError(f"block mask on {block_mask.device}, q on "
+                             f"{q.device}")
+        if key_mask is not None:
+            key_mask = _key_mask_for(key_mask, q)
+        return pack_block_mask(block_mask, B, Sq, Sk, key_mask)
+    if key_mask is not None:
+        raise ValueError("a packed BlockMask takes no separate key_mask=: "
+                         "the key mask belongs in the pack "
+                         "(pack_block_mask(..., key_mask=))")
+    bm = block_mask
+    if (bm.batch, bm.Sq, bm.Sk) != (B, Sq, Sk):
+        raise ValueError(
+            f"BlockMask was packed for (B, Sq, Sk) = "
+            f"{(bm.batch, bm.Sq, bm.Sk)}, this call has {(B, Sq, Sk)}")
+    if bm.block.device != q.device:
+        raise ValueError(f"block mask on {bm.block.device}, q on {q.device}")
+    if q.is_cuda and bm.live is None:
+        # packed on CPU (or under PA_ALLOW_EAGER) and moved: pack here
+        bm = pack_block_mask(bm.block, B, Sq, Sk, bm.keys)
+    return bm
+
+
+def _mask_for(key_mask, block_mask, q, Sq: int, Sk: int):
+    """The call's packed mask: None, a KeyMask or a BlockMask (which holds
+    the key mask too)."""
+    if block_mask is not None:
+        return _block_mask_for(block_mask, key_mask, q, Sq, Sk)
+    return None if key_mask is None else _key_mask_for(key_mask, q)
+
+
+def _mask_kw(km) -> dict:
+    """``km`` as keyword arguments of reference.attention / ops.attention*."""
+    if isinstance(km, BlockMask):
+        return {"key_mask": km.keys, "block_mask": km.block}
+    return {"key_mask": None if km is None else km.mask}
+
+
+def _attn_native(q, k, v, scale: float, km, bshd: bool,
                  split: Optional[int] = None):
     """One attention call on the native kernels: (output, None), or
     (None, why) when the call is not covered. ``why`` is None when there
     is no extension to ask (PA_ALLOW_EAGER).
 
-    Picks ext.attn_fwd[_bshd][_split][_masked]. Head dims 64/128 run as they
-    are; other 16-bit head dims under 128 are zero-padded up, on the plain
-    BSHD op only (see attention_bshd)."""
+    Picks ext.attn_fwd[_bshd][_split][_masked]; ``km`` is None, a KeyMask or
+    a BlockMask, whose 3-D ``live`` selects the block-list kernels inside
+    the masked entry points. Head dims 64/128 run as they are; other 16-bit
+    head dims under 128 are zero-padded up, on the plain BSHD op only (see
+    attention_bshd)."""
     name = ("attn_fwd" + ("_bshd" if bshd else "")
             + ("_split" if split is not None else "")
             + ("_masked" if km is not None else ""))
@@ -249,26 +399,29 @@ def _attn_native(q, k, v, scale: float, km: Optional[KeyMask], bshd: bool,
 
 
 def attention(q, k, v, scale: Optional[float] = None,
-              key_mask=None) -> torch.Tensor:
+              key_mask=None, block_mask=None) -> torch.Tensor:
     """Flash-style fused attention, layout [B, H, S, D].
 
     key_mask: optional KeyMask or raw [B, Sk] bool/integer mask (see
-    pack_key_mask for the contract)."""
+    pack_key_mask for the contract).
+    block_mask: optional BlockMask or raw [ceil(Sq/256), ceil(Sk/64)]
+    bool/integer mask (see pack_block_mask for the contract). A raw one is
+    packed per call, together with key_mask; a packed one already holds its
+    key mask, and passing key_mask= beside it raises."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    km = None if key_mask is None else _key_mask_for(key_mask, q)
+    km = _mask_for(key_mask, block_mask, q, q.shape[2], k.shape[2])
     if q.is_cuda:
         out, why = _attn_native(q, k, v, scale, km, bshd=False)
         if out is not None:
             return out
         if why is not None:
             _unsupported("attn_fwd", why)
-    return reference.attention(q, k, v, scale,
-                               None if km is None else km.mask)
+    return reference.attention(q, k, v, scale, **_mask_kw(km))
 
 
 def attention_bshd(q, k, v, scale: Optional[float] = None,
-                   key_mask=None) -> torch.Tensor:
+                   key_mask=None, block_mask=None) -> torch.Tensor:
     """Fused attention on [B, S, H, D] (strided views allowed — e.g. slices
     of a fused qkv projection; no transpose/contiguous copies on GPU).
 
@@ -277,7 +430,8 @@ def attention_bshd(q, k, v, scale: Optional[float] = None,
     columns are sliced off the output.
 
     key_mask: optional KeyMask or raw [B, Sk] bool/integer mask (see
-    pack_key_mask for the contract).
+    pack_key_mask for the contract). block_mask: optional BlockMask or raw
+    [ceil(Sq/256), ceil(Sk/64)] mask, as in attention.
 
     Cost statement: the pad wastes attention FLOPs
     proportional to Dp/D — 60% at D=40->64, 60% at D=80->128 — plus one
@@ -290,7 +444,7 @@ def attention_bshd(q, k, v, scale: Optional[float] = None,
     """
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    km = None if key_mask is None else _key_mask_for(key_mask, q)
+    km = _mask_for(key_mask, block_mask, q, q.shape[1], k.shape[1])
     if q.is_cuda:
         out, why = _attn_native(q, k, v, scale, km, bshd=True)
         if out is not None:
@@ -299,19 +453,19 @@ def attention_bshd(q, k, v, scale: Optional[float] = None,
             _unsupported("attn_fwd_bshd", why)
     out = reference.attention(
         q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3),
-        scale, None if km is None else km.mask,
+        scale, **_mask_kw(km),
     )
     return out.permute(0, 2, 1, 3)
 
 
 def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None,
-                         key_mask=None):
+                         key_mask=None, block_mask=None):
     """attention_bshd with per-stream outputs: rows [:split] and [split:]
     land in two contiguous tensors (feeds dual-stream projections with no
-    reshape copies). key_mask as in attention_bshd."""
+    reshape copies). key_mask and block_mask as in attention_bshd."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    km = None if key_mask is None else _key_mask_for(key_mask, q)
+    km = _mask_for(key_mask, block_mask, q, q.shape[1], k.shape[1])
     if q.is_cuda:
         out, why = _attn_native(q, k, v, scale, km, bshd=True, split=split)
         if out is not None:
@@ -326,7 +480,10 @@ def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None,
         if km is None and not padded:
             _unsupported("attn_fwd_bshd_split",
                          f"dtype={q.dtype}, D={q.shape[-1]}")
-    out = attention_bshd(q, k, v, scale, km)
+    if isinstance(km, BlockMask):
+        out = attention_bshd(q, k, v, scale, block_mask=km)
+    else:
+        out = attention_bshd(q, k, v, scale, km)
     return out[:, :split].contiguous(), out[:, split:].contiguous()
 
 

@@ -1,5 +1,5 @@
-// Fused attention forward: key-mask pack, the v4 kernel, the one launcher
-// and the six entry points.
+// Fused attention forward: key-mask and block-mask packs, the v4 kernel, the
+// one launcher and the six entry points.
 #pragma once
 
 using bf16x8 = short8;
@@ -95,6 +95,81 @@ std::vector<at::Tensor> pack_key_mask(at::Tensor mask) {
 }
 
 // ---------------------------------------------------------------------------
+// Block-mask pack: [nq, nk] bool block mask (nonzero = query block qb attends
+// key tile t; 256 query rows by 64 keys, shared by batch and heads) plus the
+// key-mask words of pack_key_mask_kernel -> one live list per (b, qb), which
+// the QLIST attention instantiations read.
+//   live[b][qb][..]  ascending tiles t with block[qb][t] != 0 and
+//                    words[b][t] != 0, compacted to the front (zero tail)
+//   nlive[b][qb]     how many
+// A block-live tile whose word is 0 is dropped, so every listed tile holds a
+// live key, as the kernel's sentinel arithmetic needs. One wave per (qb, b),
+// 64 tiles per step with the ballot + prefix popcount of the key-mask pack's
+// wave 0. No host read: graph-capturable behind pack_key_mask_kernel on the
+// same stream.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void pack_block_lists_kernel(
+    const unsigned char* __restrict__ block,
+    const unsigned long long* __restrict__ words, int* __restrict__ live,
+    int* __restrict__ nlive, int nq, int n_tiles) {
+    const int qb = blockIdx.x;
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x;
+    const unsigned char* bm = block + (long)qb * n_tiles;
+    const unsigned long long* wb = words + (long)b * n_tiles;
+    const long row = (long)b * nq + qb;
+    int* lb = live + row * n_tiles;
+    int count = 0;
+    for (int base = 0; base < n_tiles; base += 64) {
+        const int t = base + lane;
+        const bool alive = t < n_tiles && bm[t] != 0 && wb[t] != 0ull;
+        const unsigned long long m = __ballot(alive);
+        if (alive)
+            lb[count + __popcll(m & ((1ull << lane) - 1ull))] = t;
+        count += __popcll(m);
+    }
+    for (int i = count + lane; i < n_tiles; i += 64) lb[i] = 0;
+    if (lane == 0) nlive[row] = count;
+}
+
+// block: [nq, nk] bool/integer; words: [B, nk] from pack_key_mask.
+std::vector<at::Tensor> pack_block_lists(at::Tensor block, at::Tensor words) {
+    CHECK_GPU(block);
+    CHECK_GPU(words);
+    TORCH_CHECK(block.dim() == 2,
+                "pack_block_lists expects a [nq, nk] block mask");
+    TORCH_CHECK(block.scalar_type() == at::kBool ||
+                    at::isIntegralType(block.scalar_type(), false),
+                "pack_block_lists: bool or integer block mask only (nonzero "
+                "= attend); additive float biases are not supported, got ",
+                block.scalar_type());
+    TORCH_CHECK(words.device() == block.device(),
+                "pack_block_lists: words must be on the block mask's device");
+    TORCH_CHECK(words.dim() == 2 && words.scalar_type() == at::kLong &&
+                    words.is_contiguous(),
+                "pack_block_lists: words must be contiguous [B, nk] int64 "
+                "(pack_key_mask's)");
+    TORCH_CHECK(words.size(1) == block.size(1),
+                "pack_block_lists: block mask has ", block.size(1),
+                " key tiles, words have ", words.size(1));
+    auto bm = (block.scalar_type() == at::kBool ? block : block.ne(0))
+                  .contiguous();
+    const int nq = (int)bm.size(0), n_tiles = (int)bm.size(1);
+    const int B = (int)words.size(0);
+    TORCH_CHECK(B <= 65535, "pack_block_lists: batch ", B, " exceeds 65535");
+    auto live = at::empty({B, nq, n_tiles}, bm.options().dtype(at::kInt));
+    auto nlive = at::empty({B, nq}, bm.options().dtype(at::kInt));
+    if (B > 0 && nq > 0)
+        hipLaunchKernelGGL(pack_block_lists_kernel,
+                           dim3((unsigned)nq, (unsigned)B), dim3(64), 0,
+                           cur_stream(), (const unsigned char*)bm.data_ptr(),
+                           (const unsigned long long*)words.data_ptr(),
+                           live.data_ptr<int>(), nlive.data_ptr<int>(), nq,
+                           n_tiles);
+    return {live, nlive};
+}
+
+// ---------------------------------------------------------------------------
 // Attention v4: swapped-QK^T 32x32 structure (guide Appendix B ladder).
 //
 // mfma_f32_32x32x16_bf16 computing S^T = K·Q^T, so each LANE owns a full
@@ -140,7 +215,13 @@ std::vector<at::Tensor> pack_key_mask(at::Tensor mask) {
 // (see "KV loop" in the body); `if constexpr (MASKED)` only picks where the
 // trip count, the tile index and the mask word come from, and the unmasked
 // instantiations compile to the code they had before the flag existed.
-template <int D, typename E, bool MASKED = false>
+//
+// QLIST (block masks, needs MASKED; see pack_block_lists_kernel): the live
+// list and its count belong to (batch element, query block) instead of the
+// batch element — row b * nq + qtile of live/nlive instead of row b. qtile
+// is block-uniform, so everything above holds unchanged; the mask words stay
+// per batch element. Nothing else differs from MASKED.
+template <int D, typename E, bool MASKED = false, bool QLIST = false>
 __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     const E* __restrict__ q, const E* __restrict__ k,
     const E* __restrict__ v, E* __restrict__ out,
@@ -418,6 +499,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     // the masked and unmasked instantiations share it:
     //   nt          trip count: nlive[b] (MASKED) or n_tiles
     //   tile_at(j)  j-th tile to process: live[b][j] (MASKED) or j
+    // (QLIST: read nlive[b][qtile] and live[b][qtile][j] for these two)
     //   word_of(t)  tile t's 64-bit mask word (MASKED) or 0 (ignored)
     // b is uniform across the block, so are nt, every tile index and every
     // mask word: readfirstlane pins them in SGPRs, and trip counts and
@@ -425,11 +507,14 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     // loads, LDS writes and barrier too; the unmasked prologue is
     // unconditional, as it was before the flag existed.
     const int n_tiles = (Sk + KVBLK - 1) / KVBLK;
-    const int* live_b = MASKED ? mask_live + b * n_tiles : nullptr;
+    // row of live/nlive: per batch element, or per (b, query block)
+    const long lrow =
+        QLIST ? b * ((S + WAVES * 32 - 1) / (WAVES * 32)) + qtile : b;
+    const int* live_b = MASKED ? mask_live + lrow * n_tiles : nullptr;
     const unsigned long long* words_b =
         MASKED ? mask_words + b * n_tiles : nullptr;
     const int nt =
-        MASKED ? __builtin_amdgcn_readfirstlane(mask_nlive[b]) : n_tiles;
+        MASKED ? __builtin_amdgcn_readfirstlane(mask_nlive[lrow]) : n_tiles;
     auto tile_at = [&](int j) {
         if constexpr (MASKED)
             return __builtin_amdgcn_readfirstlane(live_b[j]);
@@ -545,7 +630,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     }
 }
 
-// Packed key mask as the MASKED kernels take it (see pack_key_mask).
+// Packed key mask as the MASKED kernels take it (see pack_key_mask). With a
+// block mask, live is [B, nq, nk] and nlive [B, nq] (see pack_block_lists),
+// which selects the QLIST instantiations.
 struct AttnKeyMask {
     at::Tensor words, live, nlive;
 };
@@ -574,10 +661,10 @@ struct AttnArgs {
     const int *mask_live, *mask_nlive;
 };
 
-template <int D, bool MASKED>
+template <int D, bool MASKED, bool QLIST = false>
 static void launch_attn_v4(at::ScalarType st, dim3 grid, const AttnArgs& a) {
     PA_WITH_ELEM16(st, hipLaunchKernelGGL(
-        HIP_KERNEL_NAME(attn_fwd_v4_kernel<D, E, MASKED>), grid, dim3(512), 0,
+        HIP_KERNEL_NAME(attn_fwd_v4_kernel<D, E, MASKED, QLIST>), grid, dim3(512), 0,
         cur_stream(), (const E*)a.q, (const E*)a.k, (const E*)a.v, (E*)a.out,
         a.S, a.Sk, a.scale, a.H, a.q_bs, a.q_hs, a.q_ss, a.k_bs, a.k_hs,
         a.k_ss, a.v_bs, a.v_hs, a.v_ss, a.o_bs, a.o_hs, a.o_ss, a.xcd_grid,
@@ -586,7 +673,8 @@ static void launch_attn_v4(at::ScalarType st, dim3 grid, const AttnArgs& a) {
 }
 
 // The one attention launcher. split > 0 (bshd only) writes rows >= split to
-// a second tensor; km != nullptr selects the MASKED instantiations.
+// a second tensor; km != nullptr selects the MASKED instantiations, and a
+// 3-D km->live their QLIST flavour.
 static std::vector<at::Tensor> attn_fwd_launch(
     at::Tensor q, at::Tensor k, at::Tensor v, double scale, bool bshd,
     long split, const AttnKeyMask* km) {
@@ -624,15 +712,25 @@ static std::vector<at::Tensor> attn_fwd_launch(
                         km->live.scalar_type() == at::kInt &&
                         km->nlive.scalar_type() == at::kInt,
                     "attn_fwd: key mask needs int64 words, int32 live/nlive");
-        TORCH_CHECK(km->words.dim() == 2 && km->live.dim() == 2 &&
-                        km->nlive.dim() == 1 && km->words.size(0) == B &&
-                        km->live.size(0) == B && km->nlive.size(0) == B,
+        const bool qlist = km->live.dim() == 3;
+        TORCH_CHECK(km->words.dim() == 2 &&
+                        (km->live.dim() == 2 || km->live.dim() == 3) &&
+                        km->nlive.dim() == km->live.dim() - 1 &&
+                        km->words.size(0) == B && km->live.size(0) == B &&
+                        km->nlive.size(0) == B,
                     "attn_fwd: key mask batch must equal q's batch (", B, ")");
         TORCH_CHECK(km->words.size(1) == n_tiles &&
-                        km->live.size(1) == n_tiles,
+                        km->live.size(qlist ? 2 : 1) == n_tiles,
                     "attn_fwd: key mask was packed for another Sk (", Sk,
                     " keys need ", n_tiles, " tiles, got ",
                     km->words.size(1), ")");
+        if (qlist) {
+            const long nqb = (S + 255) / 256;
+            TORCH_CHECK(km->live.size(1) == nqb && km->nlive.size(1) == nqb,
+                        "attn_fwd: block mask was packed for another Sq (", S,
+                        " rows need ", nqb, " query blocks, got ",
+                        km->live.size(1), ")");
+        }
         TORCH_CHECK(km->words.is_contiguous() && km->live.is_contiguous() &&
                         km->nlive.is_contiguous(),
                     "attn_fwd: key mask tensors must be contiguous");
@@ -664,7 +762,10 @@ static std::vector<at::Tensor> attn_fwd_launch(
         km ? km->live.data_ptr<int>() : nullptr,
         km ? km->nlive.data_ptr<int>() : nullptr};
     const at::ScalarType st = qc.scalar_type();
-    if (km != nullptr) {
+    if (km != nullptr && km->live.dim() == 3) {
+        if (D == 128) launch_attn_v4<128, true, true>(st, grid, a);
+        else launch_attn_v4<64, true, true>(st, grid, a);
+    } else if (km != nullptr) {
         if (D == 128) launch_attn_v4<128, true>(st, grid, a);
         else launch_attn_v4<64, true>(st, grid, a);
     } else {

@@ -45,6 +45,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "Attention with per-stream split outputs [B,:split]/[B,split:]");
     m.def("pack_key_mask", &pack_key_mask,
           "[B,Sk] bool/int key mask -> (words, live tile list, nlive)");
+    m.def("pack_block_lists", &pack_block_lists,
+          "[nq,nk] block mask + key-mask words -> per-(b, q-block) live "
+          "tile lists [B,nq,nk] and counts [B,nq]");
     m.def("attn_fwd_masked", &attn_fwd_masked,
           "attn_fwd with a packed key-padding mask (dead tiles skipped)");
     m.def("attn_fwd_bshd_masked", &attn_fwd_bshd_masked,

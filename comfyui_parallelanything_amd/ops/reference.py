@@ -115,9 +115,36 @@ def as_bool_key_mask(mask: torch.Tensor) -> torch.Tensor:
     return mask if mask.dtype == torch.bool else mask != 0
 
 
+# Block-mask granularity: the attention kernel's geometry, 256 query rows by
+# 64 keys (ops.ATTN_Q_BLOCK / ops.ATTN_KV_TILE).
+Q_BLOCK = 256
+KV_TILE = 64
+
+
+def block_mask_shape(Sq: int, Sk: int) -> Tuple[int, int]:
+    return (Sq + Q_BLOCK - 1) // Q_BLOCK, (Sk + KV_TILE - 1) // KV_TILE
+
+
+def as_bool_block_mask(mask: torch.Tensor, Sq: int, Sk: int) -> torch.Tensor:
+    """[ceil(Sq/256), ceil(Sk/64)] bool/integer block mask (nonzero = the
+    query block attends the key tile) -> bool. Floating masks are refused
+    for as_bool_key_mask's reason; another shape raises ValueError."""
+    if mask.dtype.is_floating_point or mask.dtype.is_complex:
+        raise ValueError(
+            f"block mask must be bool or integer (nonzero = attend), got "
+            f"{mask.dtype}: additive float biases are not supported")
+    want = block_mask_shape(Sq, Sk)
+    if tuple(mask.shape) != want:
+        raise ValueError(
+            f"block mask must be [ceil(Sq/{Q_BLOCK}), ceil(Sk/{KV_TILE})] = "
+            f"{list(want)} for Sq={Sq}, Sk={Sk}, got {list(mask.shape)}")
+    return mask if mask.dtype == torch.bool else mask != 0
+
+
 def attention(
     q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None,
     key_mask: Optional[torch.Tensor] = None,
+    block_mask: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Plain attention, [B, H, S, D] -> [B, H, S, D]. fp32 softmax.
 
@@ -125,10 +152,39 @@ def attention(
     rows are don't-care (zeroed before the matmuls, so NaN/Inf there never
     reaches the result), masked scores go to -inf, and a batch element with
     no live key gives zeros.
+
+    block_mask: optional [ceil(Sq/256), ceil(Sk/64)] bool/integer, shared by
+    batch and heads; nonzero = the 256-row query block attends the 64-key
+    tile. Key j is visible to query row i of batch element b iff
+    block_mask[i // 256][j // 64] and (no key mask or key_mask[b][j]). K/V
+    rows at keys no query row of that batch element sees are don't-care
+    (zeroed before the matmuls), and a query row with no visible key gives
+    zeros.
     """
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     dtype = q.dtype
+    if block_mask is not None:
+        Sq, Sk = q.shape[2], k.shape[2]
+        bm = as_bool_block_mask(block_mask, Sq, Sk).to(q.device)
+        vis = bm.repeat_interleave(Q_BLOCK, dim=0).repeat_interleave(
+            KV_TILE, dim=1)[None, None, :Sq, :Sk]       # [1, 1, Sq, Sk]
+        if key_mask is not None:
+            m = as_bool_key_mask(key_mask).to(q.device)
+            if m.shape != (q.shape[0], Sk):
+                raise ValueError(f"key mask {tuple(m.shape)} does not match "
+                                 f"[B={q.shape[0]}, Sk={Sk}]")
+            vis = vis & m[:, None, None, :]             # [B, 1, Sq, Sk]
+        seen = vis.any(dim=2)[..., None]                # [B|1, 1, Sk, 1]
+        kf = torch.where(seen, k.float(), torch.zeros((), device=k.device))
+        vf = torch.where(seen, v.float(), torch.zeros((), device=v.device))
+        s = torch.matmul(q.float(), kf.transpose(-1, -2)) * scale
+        s = s.masked_fill(~vis, float("-inf"))
+        p = torch.softmax(s, dim=-1)
+        # a row with no visible key: softmax over all -inf is NaN -> zeros
+        p = torch.where(vis.any(dim=3, keepdim=True), p,
+                        torch.zeros((), device=p.device))
+        return torch.matmul(p, vf).to(dtype)
     if key_mask is None:
         s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
         p = torch.softmax(s, dim=-1)

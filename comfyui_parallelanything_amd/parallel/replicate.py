@@ -44,7 +44,7 @@ def _iter_tensors(module: nn.Module):
 # Device-bound runtime caches that must never be shared across replicas.
 # In-tree models keep per-device caches in dicts with these names; they are
 # reset on the new replica so it repopulates on its own GPU.
-CACHE_ATTRS = ("_pe_cache", "_mod_cache")
+CACHE_ATTRS = ("_pe_cache", "_mod_cache", "_mask_cache")
 
 # Foreign-model cache attr names, matching the reference's scrub list
 # (clear_flux_caches, any_device_parallel.py:166-195, list at :167-174):

@@ -13,7 +13,15 @@ stops after the attention section (for dtype A/B runs).
 mask, packed once outside the timed loop as the models do per forward:
 full = all keys live (the masked kernel's overhead against none), lens = the
 first --live-keys keys of every batch element live (tile skipping). TF/s
-always counts the dense Sq x Sk problem, so it is comparable across modes."""
+always counts the dense Sq x Sk problem, so it is comparable across modes.
+
+--frames F runs one shape instead of the table: WAN 720p self-attention, B1
+H40 D128 over S = F x 3600 tokens (F = 21 gives 75 600). --block-mask
+{none,full,frame:W} adds a block mask, packed once outside the timed loop
+(with the key mask, if any): full = every block live (the block-list
+kernel's overhead against --key-mask full), frame:W = the frame window of
+ops.frame_window_block_mask (needs --frames). The mask density — live
+256x64 blocks over all blocks — is printed beside each time."""
 import argparse
 import sys
 import time
@@ -48,20 +56,35 @@ def main():
                     default="none")
     ap.add_argument("--live-keys", type=int, default=64,
                     help="live keys per batch element for --key-mask lens")
+    ap.add_argument("--block-mask", default="none", metavar="none|full|frame:W")
+    ap.add_argument("--frames", type=int, default=0,
+                    help="run the WAN 720p shape with this many latent "
+                         "frames (3600 tokens each) instead of the table")
     args = ap.parse_args()
+    window = None
+    if args.block_mask.startswith("frame:"):
+        window = int(args.block_mask.split(":", 1)[1])
+        if args.frames <= 0:
+            ap.error("--block-mask frame:W needs --frames")
+    elif args.block_mask not in ("none", "full"):
+        ap.error("--block-mask takes none, full or frame:W")
     dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
     assert torch.cuda.is_available()
     dev = "cuda"
     print(f"== attention ({args.dtype}, random data, "
-          f"key mask: {args.key_mask}) ==")
-    for name, (B, H, S, Sk, D) in {
+          f"key mask: {args.key_mask}, block mask: {args.block_mask}) ==")
+    tokens_per_frame = 3600  # 720p: (720/16) x (1280/16) latent patches
+    video = {f"wan720p_f{args.frames}": (
+        1, 40, args.frames * tokens_per_frame,
+        args.frames * tokens_per_frame, 128)}
+    for name, (B, H, S, Sk, D) in (video if args.frames > 0 else {
         "flux_b8": (8, 24, 4608, 4608, 128),
         "flux_b1": (1, 24, 4608, 4608, 128),
         "sdxl_mid": (4, 20, 1024, 1024, 64),
         "square_2k": (16, 16, 2048, 2048, 128),
         "zimage_b21": (21, 28, 4352, 4352, 128),  # joint 256 txt + 4096 img
         "cross_512": (21, 28, 4096, 512, 128),    # padded text context
-    }.items():
+    }).items():
         q = torch.randn(B, H, S, D, device=dev, dtype=dtype)
         k = torch.randn(B, H, Sk, D, device=dev, dtype=dtype)
         v = torch.randn_like(k)
@@ -70,10 +93,19 @@ def main():
             live = Sk if args.key_mask == "full" else min(args.live_keys, Sk)
             km = ops.pack_key_mask(
                 (torch.arange(Sk, device=dev) < live).expand(B, Sk))
-        dt = timeit(lambda: ops.attention(q, k, v, key_mask=km), iters=10)
+        mk = {"key_mask": km}
+        note = ""
+        if args.block_mask != "none":
+            nq, nk = ops.reference.block_mask_shape(S, Sk)
+            block = (torch.ones(nq, nk, dtype=torch.bool, device=dev)
+                     if window is None else ops.frame_window_block_mask(
+                         args.frames, tokens_per_frame, window, device=dev))
+            mk = {"block_mask": ops.pack_block_mask(block, B, S, Sk, km)}
+            note = f"  density {block.float().mean().item():.4f}"
+        dt = timeit(lambda: ops.attention(q, k, v, **mk), iters=10)
         tf = attn_flops(B, H, S, D, Sk) / dt / 1e12
         print(f"  {name:10s} B{B} H{H} S{S} Sk{Sk} D{D}: {dt*1e3:8.2f} ms  "
-              f"{tf:7.1f} TF/s")
+              f"{tf:7.1f} TF/s{note}")
     if args.attn_only:
         return
 
