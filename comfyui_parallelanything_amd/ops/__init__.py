@@ -361,6 +361,23 @@ def _mask_kw(km) -> dict:
     return {"key_mask": None if km is None else km.mask}
 
 
+def _softmax_scale(q, scale: Optional[float]) -> float:
+    """The call's softmax scale: 1/sqrt(D) by default, else ``scale``, which
+    must be positive. The native kernels track the raw score maximum and
+    apply the scale afterwards ("max commutes with a positive scale"), and
+    their dead-key sentinel is a large negative raw score: with scale < 0
+    the running maximum is the scaled minimum and the output is inf/NaN,
+    with scale == 0 dead keys of a partial tile weigh as much as live ones.
+    Refused on every device, so CPU and GPU runs take the same arguments."""
+    if scale is None:
+        return 1.0 / math.sqrt(q.shape[-1])
+    scale = float(scale)
+    if not (scale > 0.0 and math.isfinite(scale)):
+        raise ValueError(f"attention scale must be positive and finite, "
+                         f"got {scale}")
+    return scale
+
+
 def _attn_native(q, k, v, scale: float, km, bshd: bool,
                  split: Optional[int] = None):
     """One attention call on the native kernels: (output, None), or
@@ -408,8 +425,7 @@ def attention(q, k, v, scale: Optional[float] = None,
     bool/integer mask (see pack_block_mask for the contract). A raw one is
     packed per call, together with key_mask; a packed one already holds its
     key mask, and passing key_mask= beside it raises."""
-    if scale is None:
-        scale = 1.0 / math.sqrt(q.shape[-1])
+    scale = _softmax_scale(q, scale)
     km = _mask_for(key_mask, block_mask, q, q.shape[2], k.shape[2])
     if q.is_cuda:
         out, why = _attn_native(q, k, v, scale, km, bshd=False)
@@ -442,8 +458,7 @@ def attention_bshd(q, k, v, scale: Optional[float] = None,
     threads) — not worth the schedule split while no headline depends on
     these shapes.
     """
-    if scale is None:
-        scale = 1.0 / math.sqrt(q.shape[-1])
+    scale = _softmax_scale(q, scale)
     km = _mask_for(key_mask, block_mask, q, q.shape[1], k.shape[1])
     if q.is_cuda:
         out, why = _attn_native(q, k, v, scale, km, bshd=True)
@@ -463,8 +478,7 @@ def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None,
     """attention_bshd with per-stream outputs: rows [:split] and [split:]
     land in two contiguous tensors (feeds dual-stream projections with no
     reshape copies). key_mask and block_mask as in attention_bshd."""
-    if scale is None:
-        scale = 1.0 / math.sqrt(q.shape[-1])
+    scale = _softmax_scale(q, scale)
     km = _mask_for(key_mask, block_mask, q, q.shape[1], k.shape[1])
     if q.is_cuda:
         out, why = _attn_native(q, k, v, scale, km, bshd=True, split=split)

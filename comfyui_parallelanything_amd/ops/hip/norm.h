@@ -174,10 +174,30 @@ __global__ void layer_norm_mod_kernel(const T* __restrict__ x,
     }
     // two reductions share the scratch sequentially
     float mean = block_reduce_sum<256>(s1, scratch) / (float)D;
+    // single-pass E[x^2] - mean^2 can round below zero on a (near-)constant
+    // row, and rsqrtf of that is NaN: clamp (exact whenever var >= 0)
     float var = block_reduce_sum<256>(s2, scratch) / (float)D - mean * mean;
-    const float rstd = rsqrtf(var + eps);
+    float corr = 0.f;
+    if constexpr (sizeof(T) == 4) {
+        // fp32 rows are held to 1e-5. The difference above loses mean^2 /
+        // var of fp32's digits (4e-4 off at mean 40, variance 1), and the
+        // mean itself is only good to its own rounding (2e-6 at 40). A pass
+        // over the deviations d = x - mean gives both back: var = E[d^2] -
+        // E[d]^2, and E[d] is what the mean missed.
+        float sd = 0.f, sq = 0.f;
+        for (int i = threadIdx.x; i < D; i += blockDim.x) {
+            float d = (float)xr[i] - mean;
+            sd += d;
+            sq += d * d;
+        }
+        corr = block_reduce_sum<256>(sd, scratch) / (float)D;
+        var = block_reduce_sum<256>(sq, scratch) / (float)D - corr * corr;
+    }
+    const float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
     for (int i = threadIdx.x; i < D; i += blockDim.x) {
-        float v = ((float)xr[i] - mean) * rstd;
+        float v = (float)xr[i] - mean;
+        if constexpr (sizeof(T) == 4) v -= corr;
+        v *= rstd;
         v = v * (1.f + (float)sc[i]) + (float)sh[i];
         yr[i] = (T)v;
     }
@@ -203,8 +223,9 @@ PA_DEV void ln_row_stats(const short8* xr, int D, float eps, float* scratch,
         }
     }
     mean = block_reduce_sum<256>(s[0], scratch) / (float)D;
+    // clamped for layer_norm_mod_kernel's reason
     float var = block_reduce_sum<256>(s[1], scratch) / (float)D - mean * mean;
-    rstd = rsqrtf(var + eps);
+    rstd = rsqrtf(fmaxf(var, 0.f) + eps);
 }
 
 // Normalize and modulate one element: (x - mean) * rstd * (1 + scale) + shift.
@@ -295,11 +316,26 @@ __global__ void group_norm_silu_kernel(const T* __restrict__ x,
         s2 += v * v;
     }
     float mean = block_reduce_sum<256>(s1, scratch) / (float)n;
+    // clamped, and for fp32 corrected by a pass over the deviations, for
+    // layer_norm_mod_kernel's reasons
     float var = block_reduce_sum<256>(s2, scratch) / (float)n - mean * mean;
-    const float rstd = rsqrtf(var + eps);
+    float corr = 0.f;
+    if constexpr (sizeof(T) == 4) {
+        float sd = 0.f, sq = 0.f;
+        for (long i = threadIdx.x; i < n; i += blockDim.x) {
+            float d = (float)x[base + i] - mean;
+            sd += d;
+            sq += d * d;
+        }
+        corr = block_reduce_sum<256>(sd, scratch) / (float)n;
+        var = block_reduce_sum<256>(sq, scratch) / (float)n - corr * corr;
+    }
+    const float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
     for (long i = threadIdx.x; i < n; i += blockDim.x) {
         const int c = g * cpg + (int)(i / HW);
-        float v = ((float)x[base + i] - mean) * rstd;
+        float v = (float)x[base + i] - mean;
+        if constexpr (sizeof(T) == 4) v -= corr;
+        v *= rstd;
         if (w != nullptr) v = v * w[c] + bias[c];
         out[base + i] = (T)(v / (1.f + __expf(-v)));  // SiLU
     }
