@@ -551,16 +551,28 @@ def quant_fp8(x: torch.Tensor, scale: torch.Tensor,
     The fused epilogue overwrites ``scale[0]`` with the NEXT call's scale;
     pass a separate ``scale_used`` buffer to receive a snapshot of the scale
     this call actually quantized with (what _scaled_mm must dequantize by).
-    GPU-only; used by the fp8 serving mode."""
+    GPU-only; used by the fp8 serving mode.
+
+    The emit contract, shared with ``gelu_fp8`` and ``layer_norm_mod_fp8``
+    (docs/KERNELS.md, "fp8 emit contract"): ``out = e4m3fn(y * fp32(1 /
+    scale[0]))``, rounded to nearest even (subnormal codes included, ``-0``
+    kept), saturated to +-448; ``+-inf`` gives +-448 and NaN a NaN byte.
+    With a two-slot ``amax_buf``: ``scale_used = scale``; ``amax_buf[0] =
+    max(amax_buf[0], max|y|) * 0.999``; ``scale = max(amax_buf[0] / 448,
+    1e-12)``, each one fp32 operation. NaN never enters the amax. When the
+    running amax is not finite (an inf activation) the scale stays as it
+    was and ``amax_buf[0] = scale * 448``, so one inf costs one saturated
+    call and not the layer. A one-slot ``amax_buf`` only takes the max."""
     ext = _require_ext("quant_fp8")
     return ext.quant_fp8(x, scale, amax_buf,
                          scale if scale_used is None else scale_used)
 
 
 def gelu_fp8(x, scale, amax_buf, scale_used) -> torch.Tensor:
-    """tanh-GELU emitting e4m3fn with quant_fp8's delayed-scaling contract
-    (fp8 serving mode: the MLP-down GEMM consumes the output directly,
-    no standalone quant pass). GPU-only."""
+    """tanh-GELU emitting e4m3fn with quant_fp8's emit and delayed-scaling
+    contract (fp8 serving mode: the MLP-down GEMM consumes the output
+    directly, no standalone quant pass): NaN in is a NaN byte out, +inf
+    saturates to 448. GPU-only."""
     ext = _require_ext("gelu_fp8")
     return ext.gelu_fp8(x, scale, amax_buf, scale_used)
 
@@ -590,7 +602,10 @@ def layer_norm_mod_fp8(x, scale, shift, qscale, amax_buf, scale_used,
     layer_norm_mod + quant_fp8 (two HBM round-trips -> one). Delayed
     scaling matches quant_fp8: quantizes with qscale[0], updates the
     running amax, writes the next scale, snapshots the used scale into
-    scale_used. GPU-only."""
+    scale_used; a row that holds a NaN comes out as NaN bytes and leaves
+    the amax alone. ``scale`` and ``shift`` must be [B, D] tensors of x's
+    dtype on x's device (anything else raises before the launch).
+    GPU-only."""
     ext = _require_ext("layer_norm_mod_fp8")
     return ext.layer_norm_mod_fp8(x, scale, shift, qscale, amax_buf,
                                   scale_used, float(eps))

@@ -81,12 +81,19 @@ at::Tensor gate_residual(at::Tensor res, at::Tensor gate, at::Tensor x) {
 // exp2 never overflows (E=inf would NaN; matches tanhf to 1e-15): with
 // En = exp2(-2|c|log2e) in (0,1], tanh(|c|) = (1-En)/(1+En), so
 // g = f * r or f * (1-r) with r = 1/(1+En).
+// 1 - r carries the rounding of r, half an ulp of 1 or more, whatever is
+// left of it: 1e-5 relative at x = -3 and a third of the value at x = -5.
+// A 16-bit output rounds that away (its absolute size stays below 1e-7), and
+// gelu_tanh keeps the form so that its outputs stay what they were. The fp8
+// emit divides by a scale that can be small, so kTail = true takes the same
+// factor as En * r, which has no cancellation (same instruction count).
+template <bool kTail = false>
 PA_DEV float gelu_tanh_f32(float f) {
     const float c = 0.7978845608028654f * (f + 0.044715f * f * f * f);
     const float En = __builtin_amdgcn_exp2f(-2.8853900817779268f * fabsf(c));
     // v_rcp_f32 (~1 ulp) instead of the ~10-instr IEEE divide
     const float r = __builtin_amdgcn_rcpf(1.f + En);
-    return f * (c >= 0.f ? r : 1.f - r);
+    return f * (c >= 0.f ? r : (kTail ? En * r : 1.f - r));
 }
 
 // Vectorized tanh-GELU (16-bit short8): the MLP activation between the two

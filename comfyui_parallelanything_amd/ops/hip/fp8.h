@@ -11,7 +11,14 @@
 // writes the next call's scale.
 
 // Eight values f(0..7) -> clamp(f * inv_s) to the e4m3 range, cast, one
-// 8-byte store at out[at]. f is a callable, not an array, and the address
+// 8-byte store at out[at]. The clamp is the NaN-propagating maximum/minimum
+// pair (v_maximum3_f32 / v_minimum3_f32), so NaN in is a NaN byte out and
+// +-inf saturates to +-448; fminf(fmaxf(NaN, -448), 448) is -448, the
+// largest negative code. Every value that reaches the cast is then within
+// +-448 or NaN, so the cast is asked for no saturation of its own: with
+// __HIP_SATFINITE it clamps finite values a second time behind a test for
+// inf/NaN (three instructions per element that can no longer change a
+// byte). f is a callable, not an array, and the address
 // is formed here, so the inlined code keeps the per-element order (value,
 // amax, cast, ..., address, store) the kernels were tuned with: an array
 // argument or a precomputed pointer cost 1-3 VGPRs in two of the kernels.
@@ -20,9 +27,10 @@ PA_DEV void store_fp8x8(unsigned char* out, long at, float inv_s, F&& f) {
     unsigned char pack[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const float q = fminf(fmaxf(f(j) * inv_s, -448.f), 448.f);
+        const float q = __builtin_elementwise_minimum(
+            __builtin_elementwise_maximum(f(j) * inv_s, -448.f), 448.f);
         // OCP e4m3fn cast (gfx950 format; NOT fnuz)
-        pack[j] = (unsigned char)__hip_cvt_float_to_fp8(q, __HIP_SATFINITE,
+        pack[j] = (unsigned char)__hip_cvt_float_to_fp8(q, __HIP_NOSAT,
                                                         __HIP_E4M3);
     }
     *reinterpret_cast<unsigned long long*>(&out[at]) =
@@ -60,9 +68,16 @@ PA_DEV void block_amax_to_global(float local_amax, float* scratch,
 // the preceding quantization used, decay the running amax, write the next
 // call's scale. Fixed pointers -> hipGraph-capture safe. amax_buf[1] (the
 // retired block counter) stays zero, preserving the public state contract.
+// A running amax that is not finite (an inf activation; NaN never enters
+// it) must not reach the scale, where nothing would ever bring it back:
+// the scale stays as it was and the amax restarts at scale * 448.
 __global__ void fp8_scale_finalize_kernel(float* scale, float* amax_buf,
                                           float* scale_used) {
     if (scale_used != scale) scale_used[0] = scale[0];
+    if (!(fabsf(amax_buf[0]) < INFINITY)) {
+        amax_buf[0] = scale[0] * 448.f;
+        return;
+    }
     const float next = amax_buf[0] * 0.999f;
     amax_buf[0] = next;
     scale[0] = fmaxf(next / 448.f, 1e-12f);
@@ -125,9 +140,16 @@ __global__ void quant_fp8_bf16_kernel(const bf16* __restrict__ x,
                                       float* __restrict__ scale,
                                       float* __restrict__ amax_buf,
                                       long total8) {
+    // The value is the input's own bits, so a NaN among them can be a
+    // signaling one, and fmaxf (v_max_f32 in IEEE mode) answers a signaling
+    // NaN with a quiet NaN: the thread's running amax would turn NaN and
+    // the next value replace it, dropping what came before. Quieted here,
+    // the NaN is skipped like any other. (GELU and LayerNorm compute their
+    // values, which are never signaling.)
     fp8_emit_loop(x, out, total8, scale, amax_buf,
                   (long)blockIdx.x * blockDim.x + threadIdx.x,
-                  (long)gridDim.x * blockDim.x, [](float f) { return f; });
+                  (long)gridDim.x * blockDim.x,
+                  [](float f) { return __builtin_canonicalizef(f); });
 }
 
 at::Tensor quant_fp8(at::Tensor x, at::Tensor scale, at::Tensor amax_buf,
@@ -163,7 +185,7 @@ __global__ void gelu_fp8_kernel(const bf16* __restrict__ x,
     fp8_emit_loop(x, out, total8, scale, amax_buf,
                   (long)blockIdx.x * blockDim.x + threadIdx.x,
                   (long)gridDim.x * blockDim.x,
-                  [](float f) { return gelu_tanh_f32(f); });
+                  [](float f) { return gelu_tanh_f32<true>(f); });
 }
 
 at::Tensor gelu_fp8(at::Tensor x, at::Tensor scale, at::Tensor amax_buf,
@@ -196,6 +218,7 @@ __global__ void layer_norm_mod_fp8_kernel(
     float* __restrict__ amax_buf) {
     using EL = Elem16<bf16>;
     const int DV = D / 8;
+    __shared__ double stats[8];
     __shared__ float scratch[8];
     const float inv_s = 1.0f / qscale[0];
     const long row = blockIdx.x;
@@ -205,7 +228,7 @@ __global__ void layer_norm_mod_fp8_kernel(
     const short8* sh = reinterpret_cast<const short8*>(shift + b * (long)D);
 
     float mean, rstd;
-    ln_row_stats<EL>(xr, D, eps, scratch, mean, rstd);
+    ln_row_stats_wide<EL>(xr, D, eps, stats, mean, rstd);
     float local_amax = 0.f;
     for (int i = threadIdx.x; i < DV; i += blockDim.x) {
         short8 v = xr[i], a = sc[i], c = sh[i];
@@ -215,8 +238,6 @@ __global__ void layer_norm_mod_fp8_kernel(
             return f;
         });
     }
-    // scratch reuse: stragglers may still read the reduce broadcast
-    __syncthreads();
     block_amax_to_global(local_amax, scratch, amax_buf);
 }
 
@@ -231,6 +252,13 @@ at::Tensor layer_norm_mod_fp8(at::Tensor x, at::Tensor scale, at::Tensor shift,
     auto sh = shift.contiguous();
     const int S = (int)xc.size(1), D = (int)xc.size(2);
     TORCH_CHECK((D % 8) == 0, "layer_norm_mod_fp8: D % 8 == 0");
+    CHECK_GPU(scale);
+    CHECK_GPU(shift);
+    CHECK_SAME_DTYPE(scale, x);
+    CHECK_SAME_DTYPE(shift, x);
+    TORCH_CHECK(sc.dim() == 2 && sc.size(0) == xc.size(0) && sc.size(1) == D &&
+                    sc.sizes() == sh.sizes(),
+                "layer_norm_mod_fp8: scale/shift [B, D]");
     TORCH_CHECK(amax_buf.numel() >= 2, "amax_buf needs the counter slot");
     auto out = at::empty(xc.sizes(), xc.options().dtype(at::kFloat8_e4m3fn));
     // block per row (bf16-LN geometry)

@@ -208,8 +208,7 @@ __global__ void layer_norm_mod_kernel(const T* __restrict__ x,
 // 256-thread block gets the row's mean and rstd; the two reductions share
 // `scratch` (8 floats) sequentially.
 template <typename EL>
-PA_DEV void ln_row_stats(const short8* xr, int D, float eps, float* scratch,
-                         float& mean, float& rstd) {
+PA_DEV f32x2 ln_row_sums(const short8* xr, int D) {
     // (sum, sum of squares) as one explicit pair: the compiler pairs the
     // two scalar sums into v_pk_add_f32 when the loop is written in the
     // kernel, but not when it is inlined from here
@@ -222,10 +221,52 @@ PA_DEV void ln_row_stats(const short8* xr, int D, float eps, float* scratch,
             s += f32x2{f, f * f};
         }
     }
+    return s;
+}
+
+template <typename EL>
+PA_DEV void ln_row_stats(const short8* xr, int D, float eps, float* scratch,
+                         float& mean, float& rstd) {
+    const f32x2 s = ln_row_sums<EL>(xr, D);
     mean = block_reduce_sum<256>(s[0], scratch) / (float)D;
     // clamped for layer_norm_mod_kernel's reason
     float var = block_reduce_sum<256>(s[1], scratch) / (float)D - mean * mean;
     rstd = rsqrtf(fmaxf(var, 0.f) + eps);
+}
+
+// The same statistics with the two sums reduced across the block, and the
+// variance taken, in fp64 (layer_norm_mod_fp8_kernel). var = E[x^2] - mean^2
+// loses mean^2 / var of the digits it is computed in: on a row of mean 40
+// and variance 1 the fp32 form leaves rstd 5e-5 to 1.5e-4 off, which a
+// 16-bit output rounds away but the fp8 emit carries into its running amax
+// and from there into the next scale. The per-thread sums stay fp32, the
+// loop above: a thread adds at most D / 2048 vectors, and where the
+// cancellation is large the row's values share a binade or two, so the
+// squares of bf16 values (16 bits) add exactly in 24. `scratch` holds two
+// doubles per wave; one exchange instead of two.
+template <typename EL>
+PA_DEV void ln_row_stats_wide(const short8* xr, int D, float eps,
+                              double* scratch, float& mean, float& rstd) {
+    const f32x2 s = ln_row_sums<EL>(xr, D);
+    double s1 = s[0], s2 = s[1];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s1 += __shfl_xor(s1, off, 64);
+        s2 += __shfl_xor(s2, off, 64);
+    }
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wid = threadIdx.x / WAVE;
+    if (lane == 0) {
+        scratch[2 * wid] = s1;
+        scratch[2 * wid + 1] = s2;
+    }
+    __syncthreads();
+    s1 = (scratch[0] + scratch[2]) + (scratch[4] + scratch[6]);
+    s2 = (scratch[1] + scratch[3]) + (scratch[5] + scratch[7]);
+    const double inv_d = 1.0 / (double)D;
+    const double m = s1 * inv_d;
+    mean = (float)m;
+    rstd = rsqrtf(fmaxf((float)(s2 * inv_d - m * m), 0.f) + eps);
 }
 
 // Normalize and modulate one element: (x - mean) * rstd * (1 + scale) + shift.

@@ -529,15 +529,19 @@ def gelu_values(dtype):
 # mean^2 clamped at 0, rstd = rsqrt(var + eps). fused=True rounds x*x + s2
 # once (fma), fused=False twice: the compiler may pick either.
 #
+# wide=True is ln_row_stats_wide (layer_norm_mod_fp8_kernel): the per-thread
+# fp32 sums are added across the block, and the variance taken, in fp64.
+#
 # fault: None, "no_eps", "eps_outside", "no_mean", "no_clamp", "skip_last"
 # --------------------------------------------------------------------------
 
 NORM_FAULTS = ("no_eps", "eps_outside", "no_mean", "no_clamp", "skip_last")
 
 
-def _block_sum(vals, fused_sq=None):
+def _block_sum(vals, fused_sq=None, wide=False):
     """vals [rows, nvec, vec] fp32 -> [rows]; vector i belongs to thread
-    i % 256. fused_sq: add the squares, with one rounding per add."""
+    i % 256. fused_sq: add the squares, with one rounding per add. wide:
+    the 256 thread sums added in fp64, returned as fp64."""
     rows, nvec, vec = vals.shape
     passes_ = (nvec + 255) // 256
     pad = passes_ * 256 - nvec
@@ -553,6 +557,8 @@ def _block_sum(vals, fused_sq=None):
                 acc = (acc.double() + x.double() * x.double()).float()
             else:
                 acc = acc + x * x
+    if wide:
+        return acc.double().sum(1)
     w = acc.view(rows, 4, 64)
     for off in (32, 16, 8, 4, 2, 1):
         w = w + w[:, :, torch.arange(64) ^ off]
@@ -563,7 +569,7 @@ def _block_sum(vals, fused_sq=None):
 
 
 def emulate_row_stats(x, eps=1e-6, fault=None, fused=True, vec=8,
-                      deviation_pass=False):
+                      deviation_pass=False, wide=False):
     """x [rows, D] -> (mean, rstd, corr), fp32 [rows]. deviation_pass: the
     fp32 instantiations of the scalar kernels, which sum d = x - mean and
     d * d in a further pass: corr = E[d] is what the mean missed, var =
@@ -572,10 +578,12 @@ def emulate_row_stats(x, eps=1e-6, fault=None, fused=True, vec=8,
     xf = x.float().view(rows, D // vec, vec)
     if fault == "skip_last":
         xf = xf[:, :-1]
-    s1 = _block_sum(xf)
-    s2 = _block_sum(xf, fused_sq=fused)
+    s1 = _block_sum(xf, wide=wide)
+    s2 = _block_sum(xf, fused_sq=fused, wide=wide)
     mean = s1 / D
     var = s2 / D - mean * mean
+    if wide:
+        mean, var = mean.float(), var.float()
     corr = torch.zeros_like(mean)
     if deviation_pass:
         d = xf - mean[:, None, None]
