@@ -97,6 +97,71 @@ def _unsupported(op: str, why: str):
 
 
 # ---------------------------------------------------------------------------
+# Argument checks of the reference path. The native launchers refuse a call
+# whose shapes would make a kernel index outside a tensor (TORCH_CHECK, a
+# RuntimeError); the reference path refuses the same calls, so a CPU run
+# and a GPU run take the same arguments. docs/KERNELS.md, "Elementwise and
+# rotary contract".
+# ---------------------------------------------------------------------------
+
+def _refuse_unless(ok: bool, msg: str):
+    if not ok:
+        raise RuntimeError(msg)
+
+
+def _check_cs(op: str, cs, S: int, D: int, ref, batched: bool = False):
+    want = [S, D // 2, 2]
+    ok = list(cs.shape) == want or (
+        batched and cs.dim() == 4 and list(cs.shape[1:]) == want)
+    _refuse_unless(ok, f"{op}: cs must be [S, D/2, 2] = {want}, got "
+                       f"{list(cs.shape)}")
+    _refuse_unless(cs.device == ref.device,
+                   f"{op}: cs is on {cs.device}, the activations on "
+                   f"{ref.device}")
+
+
+def _check_norm_weight(op: str, name: str, w, D: int, ref):
+    _refuse_unless(w.dim() == 1 and w.shape[0] == D,
+                   f"{op}: {name} must be [D] = [{D}], got {list(w.shape)}")
+    _refuse_unless(w.device == ref.device,
+                   f"{op}: {name} is on {w.device}, the activations on "
+                   f"{ref.device}")
+
+
+def _check_qk(q, k, wq, wk, cs):
+    op = "qk_norm_rope_"
+    _refuse_unless(q.dim() == 4 and k.dim() == 4, f"{op}: [B,S,H,D] views")
+    D = q.shape[3]
+    _refuse_unless(D % 2 == 0, f"{op}: D must be even, got {D}")
+    _refuse_unless(k.shape == q.shape,
+                   f"{op}: k {list(k.shape)} must have q's shape "
+                   f"{list(q.shape)}")
+    _refuse_unless(k.device == q.device,
+                   f"{op}: k is on {k.device}, q on {q.device}")
+    _check_norm_weight(op, "wq", wq, D, q)
+    _check_norm_weight(op, "wk", wk, D, q)
+    _check_cs(op, cs, q.shape[1], D, q)
+
+
+def _check_pack(txt, img, weights, cs):
+    op = "pack_joint_qkv"
+    _refuse_unless(txt.dim() == 5 and img.dim() == 5,
+                   f"{op} expects [B,S,3,H,D] views")
+    B, T, _, H, D = txt.shape
+    _refuse_unless(D % 2 == 0, f"{op}: D must be even, got {D}")
+    _refuse_unless(
+        txt.shape[2] == 3 and img.shape[2] == 3
+        and (img.shape[0], img.shape[3], img.shape[4]) == (B, H, D),
+        f"{op}: txt [B,T,3,H,D] and img [B,Si,3,H,D] must share B, H and D, "
+        f"got txt {list(txt.shape)}, img {list(img.shape)}")
+    _refuse_unless(img.device == txt.device,
+                   f"{op}: img is on {img.device}, txt on {txt.device}")
+    for name, w in zip(("wq_t", "wk_t", "wq_i", "wk_i"), weights):
+        _check_norm_weight(op, name, w, D, txt)
+    _check_cs(op, cs, T + img.shape[1], D, txt)
+
+
+# ---------------------------------------------------------------------------
 # Public ops
 # ---------------------------------------------------------------------------
 
@@ -123,6 +188,21 @@ def layer_norm_mod(x, scale, shift, eps: float = 1e-6) -> torch.Tensor:
 
 
 def gate_residual(residual, gate, x) -> torch.Tensor:
+    """residual + gate * x; x and residual [B, S, D], gate [B, D] (one row
+    per batch element: a broadcast [1, D] gate, another D, or a residual of
+    another shape raises). Zero-element inputs give an empty result."""
+    if x.dim() == 3 and gate.dim() == 2 and not x.is_cuda:
+        _refuse_unless(
+            tuple(gate.shape) == (x.shape[0], x.shape[2]),
+            f"gate_residual: gate must be [B, D] = [{x.shape[0]}, "
+            f"{x.shape[2]}], got {list(gate.shape)}")
+        _refuse_unless(
+            residual.shape == x.shape,
+            f"gate_residual: residual {list(residual.shape)} must have x's "
+            f"shape {list(x.shape)}")
+        _refuse_unless(residual.dtype == x.dtype and gate.dtype == x.dtype,
+                       "gate_residual: residual and gate dtypes must match "
+                       "x's")
     if x.is_cuda:
         ext = _require_ext("gate_residual")
         if ext is not None and gate.dim() == x.dim() - 1:
@@ -148,11 +228,18 @@ def group_norm_silu(x, num_groups: int, weight=None, bias=None,
 
 
 def rope_apply(x, cs) -> torch.Tensor:
+    """Rotate adjacent pairs of x [B, H, S, D] by cs [S, D/2, 2] (cos,
+    sin; any floating dtype, any strides). An odd D or another cs shape
+    raises."""
     if x.is_cuda:
         ext = _require_ext("rope_apply")
         if ext is not None:
             return ext.rope_apply(x.contiguous(), cs.contiguous())
-    return reference.rope_apply(x, cs)
+    _refuse_unless(x.dim() == 4, "rope_apply expects [B, H, S, D]")
+    _refuse_unless(x.shape[3] % 2 == 0,
+                   f"rope_apply: D must be even, got {x.shape[3]}")
+    _check_cs("rope_apply", cs, x.shape[2], x.shape[3], x, batched=True)
+    return reference.rope_apply(x, cs.float())
 
 
 def rope_freqs(positions, dim: int, theta: float = 10000.0) -> torch.Tensor:
@@ -513,8 +600,13 @@ def qk_norm_rope_(q, k, wq, wk, cs, eps: float = 1e-6):
             ext.qk_norm_rope_(q, k, wq, wk, cs, eps)
             return q, k
         _unsupported("qk_norm_rope_", f"dtype={q.dtype}, D={q.shape[-1]}")
-    qn = reference.rms_norm(q, wq, eps).permute(0, 2, 1, 3)
-    kn = reference.rms_norm(k, wk, eps).permute(0, 2, 1, 3)
+    _check_qk(q, k, wq, wk, cs)
+    # fp32 throughout, one rounding at the end, as the kernel does: rounding
+    # the normalised row to 16 bits first costs whole spacings wherever the
+    # rotation cancels
+    cs = cs.float()
+    qn = reference.rms_norm(q.float(), wq.float(), eps).permute(0, 2, 1, 3)
+    kn = reference.rms_norm(k.float(), wk.float(), eps).permute(0, 2, 1, 3)
     q.copy_(reference.rope_apply(qn, cs).permute(0, 2, 1, 3))
     k.copy_(reference.rope_apply(kn, cs).permute(0, 2, 1, 3))
     return q, k
@@ -523,7 +615,11 @@ def qk_norm_rope_(q, k, wq, wk, cs, eps: float = 1e-6):
 def pack_joint_qkv(txt_qkv, img_qkv, wq_t, wk_t, wq_i, wk_i, cs,
                    eps: float = 1e-6):
     """Dual-stream joint qkv pack: per-stream qk RMSNorm + RoPE + contiguous
-    [B, T+Si, H, D] q/k/v in one pass (txt_qkv/img_qkv: [B,S,3,H,D] views)."""
+    [B, T+Si, H, D] q/k/v in one pass (txt_qkv/img_qkv: [B,S,3,H,D] views).
+
+    The two streams share B, H and D and may differ in every stride; T or
+    Si may be 0; the four weights are [D], cs [T+Si, D/2, 2]. Anything else
+    raises before the launch. v is copied bit for bit."""
     if txt_qkv.is_cuda:
         ext = _require_ext("pack_joint_qkv")
         if ext is not None and txt_qkv.dtype in _NATIVE16 \
@@ -532,6 +628,7 @@ def pack_joint_qkv(txt_qkv, img_qkv, wq_t, wk_t, wq_i, wk_i, cs,
                                       cs, eps)
         _unsupported("pack_joint_qkv",
                      f"dtype={txt_qkv.dtype}, D={txt_qkv.shape[-1]}")
+    _check_pack(txt_qkv, img_qkv, (wq_t, wk_t, wq_i, wk_i), cs)
     T = txt_qkv.shape[1]
     tq, tk, tv = txt_qkv.unbind(2)
     iq, ik, iv = img_qkv.unbind(2)
@@ -587,6 +684,16 @@ def gelu_tanh(x: torch.Tensor) -> torch.Tensor:
 
 def timestep_embedding(t, dim: int, max_period: float = 10000.0,
                        time_factor: float = 1000.0) -> torch.Tensor:
+    """Sinusoidal embedding of t [B] -> fp32 [B, dim], cos | sin halves and
+    a zero last column when dim is odd (dim = 1 is that column alone).
+
+    Domain: any fp32 argument t * time_factor; the cos / sin are range-
+    reduced library functions, not the hardware instructions that stop at
+    256 revolutions. Each output is within 1.5e-7 + 36.8 * |arg| * 2^-24 of
+    the fp64 value at arg = t * time_factor * freq_j, checked up to |arg| =
+    2e4 (docs/KERNELS.md, "Elementwise and rotary contract")."""
+    if t.dim() != 1:
+        raise RuntimeError(f"timestep_embedding: t [B], got {list(t.shape)}")
     if t.is_cuda:
         ext = _require_ext("timestep_embedding")
         if ext is not None:
@@ -617,7 +724,8 @@ def timestep_embed_mlp(t, w1, b1, max_period: float = 10000.0,
 
     SURVEY §2b timestep-MLP fusion (the in_layer half; the out Linear is a
     GEMM and stays on hipBLASLt). GPU-only — callers fall back to the
-    composed path on CPU (MLPEmbedder.forward_timestep)."""
+    composed path on CPU (MLPEmbedder.forward_timestep). The sinusoid has
+    timestep_embedding's argument domain and error bound."""
     ext = _require_ext("timestep_embed_mlp")
     return ext.timestep_embed_mlp(t, w1, b1, float(max_period),
                                   float(time_factor))

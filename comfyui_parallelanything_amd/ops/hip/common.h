@@ -114,6 +114,12 @@ PA_DEV float block_reduce_sum(float v, float* scratch) {
                 #t " dtype (", (t).scalar_type(), ") must match " #ref " (",  \
                 (ref).scalar_type(), ")")
 
+// ... and live on ref's device: a pointer into another device's (or the
+// host's) memory is dereferenced by the kernel as if it were local.
+#define CHECK_SAME_DEVICE(t, ref)                                             \
+    TORCH_CHECK((t).device() == (ref).device(),                               \
+                #t " is on ", (t).device(), ", " #ref " on ", (ref).device())
+
 static hipStream_t cur_stream() {
     return c10::hip::getCurrentHIPStream().stream();
 }

@@ -50,7 +50,20 @@ __global__ void gate_residual_vec_kernel(const E* __restrict__ res,
 
 at::Tensor gate_residual(at::Tensor res, at::Tensor gate, at::Tensor x) {
     CHECK_GPU(x);
-    TORCH_CHECK(x.dim() == 3 && gate.dim() == 2, "x [B,S,D], gate [B,D]");
+    TORCH_CHECK(x.dim() == 3 && gate.dim() == 2,
+                "gate_residual: x [B,S,D], gate [B,D]");
+    // the kernels index gate[b * D + d]: a broadcast [1, D] gate, or one of
+    // another D, would be read past its end
+    TORCH_CHECK(gate.size(0) == x.size(0) && gate.size(1) == x.size(2),
+                "gate_residual: gate must be [B, D] = [", x.size(0), ", ",
+                x.size(2), "], got ", gate.sizes());
+    TORCH_CHECK(res.sizes() == x.sizes(), "gate_residual: residual ",
+                res.sizes(), " must have x's shape ", x.sizes());
+    CHECK_SAME_DEVICE(res, x);
+    CHECK_SAME_DEVICE(gate, x);
+    CHECK_SAME_DTYPE(res, x);
+    CHECK_SAME_DTYPE(gate, x);
+    if (x.numel() == 0) return at::empty(x.sizes(), x.options());
     auto rc = res.contiguous();
     auto gc = gate.contiguous();
     auto xc = x.contiguous();
@@ -59,8 +72,6 @@ at::Tensor gate_residual(at::Tensor res, at::Tensor gate, at::Tensor x) {
     const int S = (int)xc.size(1), D = (int)xc.size(2);
     const int blocks = grid_1d(total);
     const auto st = xc.scalar_type();
-    CHECK_SAME_DTYPE(res, x);
-    CHECK_SAME_DTYPE(gate, x);
     if (is_elem16(st) && (D % 8) == 0) {
         PA_WITH_ELEM16(st, hipLaunchKernelGGL(
             gate_residual_vec_kernel<E>, dim3(blocks), dim3(256), 0,
@@ -122,6 +133,7 @@ __global__ void gelu_tanh_vec_kernel(const E* __restrict__ x,
 
 at::Tensor gelu_tanh(at::Tensor x) {
     CHECK_GPU(x);
+    if (x.numel() == 0) return at::empty(x.sizes(), x.options());
     // accept a 2-D-decomposable strided view: last dim contiguous, all
     // leading dims collapsible to rows with ONE stride (e.g. a last-dim
     // slice of a fused projection) — avoids a .contiguous() copy.
@@ -184,12 +196,18 @@ __global__ void rope_apply_kernel(const T* __restrict__ x,
 at::Tensor rope_apply(at::Tensor x, at::Tensor cs) {
     CHECK_GPU(x);
     TORCH_CHECK(x.dim() == 4, "rope_apply expects [B, H, S, D]");
-    TORCH_CHECK(cs.dim() == 3, "cs expects [S, D/2, 2]");
+    const int S = (int)x.size(2), D = (int)x.size(3);
+    // an odd D would pass cs.size(1) == D / 2 by truncation, and the pairs
+    // would then straddle rows
+    TORCH_CHECK(D % 2 == 0, "rope_apply: D must be even, got ", D);
+    TORCH_CHECK(cs.dim() == 3 && cs.size(0) == S && cs.size(1) == D / 2 &&
+                cs.size(2) == 2, "rope_apply: cs must be [S, D/2, 2] = [", S,
+                ", ", D / 2, ", 2], got ", cs.sizes());
+    CHECK_SAME_DEVICE(cs, x);
+    if (x.numel() == 0) return at::empty(x.sizes(), x.options());
     auto xc = x.contiguous();
     auto cc = cs.to(at::kFloat).contiguous();
     auto out = at::empty_like(xc);
-    const int S = (int)xc.size(2), D = (int)xc.size(3);
-    TORCH_CHECK((int)cc.size(0) == S && (int)cc.size(1) == D / 2, "cs shape");
     const long pairs = xc.numel() / 2;
     PA_WITH_DTYPE("rope_apply", xc.scalar_type(), hipLaunchKernelGGL(
         rope_apply_kernel<T>, dim3(grid_1d(pairs)), dim3(256), 0, cur_stream(),
@@ -201,6 +219,21 @@ at::Tensor rope_apply(at::Tensor x, at::Tensor cs) {
 // ---------------------------------------------------------------------------
 // Timestep embedding: t [B] -> out [B, dim] fp32 (cos | sin halves).
 // ---------------------------------------------------------------------------
+
+// cos and sin of a timestep argument in radians. Not __cosf / __sinf: those
+// are one multiply by 1/2pi and the hardware v_cos_f32 / v_sin_f32, which the
+// ISA defines within +-256 revolutions (+-1608 rad) only, and the callers go
+// beyond: t * time_factor is 4000 at FLUX's default guidance and up to 14610
+// under the k-diffusion samplers. (An MI355X did wrap such arguments, with
+// the error of the fp32 multiply, 3.5e-4 at 4000 rad; the manual promises
+// neither.) The library functions reduce the argument over the whole fp32
+// range. Both kernels are launch-bound (B * dim / 2 values), so the extra
+// instructions cost nothing that can be measured.
+PA_DEV void ts_cos_sin(float arg, float& c, float& s) {
+    c = cosf(arg);
+    s = sinf(arg);
+}
+
 __global__ void timestep_embedding_kernel(const float* __restrict__ t,
                                           float* __restrict__ out,
                                           int B, int dim, float max_period,
@@ -214,8 +247,10 @@ __global__ void timestep_embedding_kernel(const float* __restrict__ t,
         const int j = (int)(i % half);
         const float freq = __expf(-__logf(max_period) * (float)j / (float)half);
         const float arg = t[b] * time_factor * freq;
-        out[(long)b * dim + j] = __cosf(arg);
-        out[(long)b * dim + half + j] = __sinf(arg);
+        float c, sn;
+        ts_cos_sin(arg, c, sn);
+        out[(long)b * dim + j] = c;
+        out[(long)b * dim + half + j] = sn;
         if ((dim & 1) && j == 0) out[(long)b * dim + dim - 1] = 0.f;
     }
 }
@@ -223,8 +258,14 @@ __global__ void timestep_embedding_kernel(const float* __restrict__ t,
 at::Tensor timestep_embedding(at::Tensor t, long dim, double max_period,
                               double time_factor) {
     CHECK_GPU(t);
+    TORCH_CHECK(t.dim() == 1 && dim >= 0,
+                "timestep_embedding: t [B] and dim >= 0, got t ", t.sizes(),
+                ", dim ", dim);
     auto tc = t.to(at::kFloat).contiguous();
     const int B = (int)tc.size(0);
+    // dim 0 and 1 have no cos/sin pair: the kernel would write nothing (the
+    // odd column hangs on j == 0); dim 1 is that zero column alone
+    if (B == 0 || dim < 2) return at::zeros({B, dim}, tc.options());
     auto out = at::empty({B, dim}, tc.options());
     const int blocks = (int)std::min<long>((B * (dim / 2) + 255) / 256, 1024);
     hipLaunchKernelGGL(timestep_embedding_kernel, dim3(std::max(blocks, 1)),
@@ -259,8 +300,10 @@ __global__ void ts_embed_mlp_kernel(const float* __restrict__ t,
     for (int j = (int)threadIdx.x; j < half; j += (int)blockDim.x) {
         const float freq = __expf(-__logf(max_period) * (float)j / (float)half);
         const float arg = tv * freq;
-        emb[j] = __cosf(arg);
-        emb[half + j] = __sinf(arg);
+        float c, sn;
+        ts_cos_sin(arg, c, sn);
+        emb[j] = c;
+        emb[half + j] = sn;
     }
     __syncthreads();
     const int o = hblk * 256 + (int)threadIdx.x;
@@ -284,6 +327,9 @@ at::Tensor timestep_embed_mlp(at::Tensor t, at::Tensor w1,
     CHECK_GPU(t);
     TORCH_CHECK(w1.scalar_type() == at::kBFloat16,
                 "timestep_embed_mlp: bf16 weight");
+    TORCH_CHECK(w1.dim() == 2, "timestep_embed_mlp: w1 [H, K], got ",
+                w1.sizes());
+    CHECK_SAME_DEVICE(w1, t);
     auto tc = t.to(at::kFloat).contiguous();
     auto w1c = w1.contiguous();
     const int H = (int)w1c.size(0), K = (int)w1c.size(1);
@@ -294,11 +340,13 @@ at::Tensor timestep_embed_mlp(at::Tensor t, at::Tensor w1,
     const bf16* bias = nullptr;
     at::Tensor b1c;
     if (b1.has_value()) {
+        CHECK_SAME_DEVICE(*b1, t);
         b1c = b1->contiguous();
         TORCH_CHECK(b1c.scalar_type() == at::kBFloat16 &&
                     (int)b1c.numel() == H, "timestep_embed_mlp: bias [H] bf16");
         bias = (const bf16*)b1c.data_ptr();
     }
+    if (B == 0 || H == 0) return out;
     const int hblocks = (H + 255) / 256;
     hipLaunchKernelGGL(ts_embed_mlp_kernel, dim3(B * hblocks), dim3(256),
                        K * sizeof(float), cur_stream(), tc.data_ptr<float>(),

@@ -18,6 +18,29 @@ PA_DEV unsigned int rms_rope_pair(unsigned int u, float w0, float w1, float c,
            ((unsigned int)EL::st(a0 * s + a1 * c) << 16);
 }
 
+// What both launchers below ask of a rotary table and a norm weight before
+// the kernel indexes them by (s, pair) and by pair.
+static void check_cs_table(const char* op, const at::Tensor& cs, long S, long D,
+                           const at::Tensor& ref) {
+    TORCH_CHECK(cs.dim() == 3 && cs.size(0) == S && cs.size(1) == D / 2 &&
+                cs.size(2) == 2, op, ": cs must be [S, D/2, 2] = [", S, ", ",
+                D / 2, ", 2], got ", cs.sizes());
+    TORCH_CHECK(cs.device() == ref.device(), op, ": cs is on ", cs.device(),
+                ", the activations on ", ref.device());
+}
+
+static void check_norm_weight(const char* op, const char* name,
+                              const at::Tensor& w, long D,
+                              const at::Tensor& ref) {
+    TORCH_CHECK(w.dim() == 1 && w.size(0) == D, op, ": ", name,
+                " must be [D] = [", D, "], got ", w.sizes());
+    TORCH_CHECK(w.scalar_type() == ref.scalar_type(), op, ": ", name,
+                " dtype (", w.scalar_type(), ") must match the activations (",
+                ref.scalar_type(), ")");
+    TORCH_CHECK(w.device() == ref.device(), op, ": ", name, " is on ",
+                w.device(), ", the activations on ", ref.device());
+}
+
 // ---------------------------------------------------------------------------
 // Fused qk-norm + RoPE (in-place): per (b, s, h) row of q and k,
 // RMSNorm over D with per-head-dim weight, then rotary by cs[s].
@@ -95,18 +118,22 @@ void qk_norm_rope_(at::Tensor q, at::Tensor k, at::Tensor wq, at::Tensor wk,
     TORCH_CHECK(is_elem16(q.scalar_type()),
                 "qk_norm_rope_: bf16 or fp16 only, got ", q.scalar_type());
     CHECK_SAME_DTYPE(k, q);
-    CHECK_SAME_DTYPE(wq, q);
-    CHECK_SAME_DTYPE(wk, q);
-    TORCH_CHECK(q.stride(3) == 1 && k.stride(3) == 1, "last dim contiguous");
+    CHECK_SAME_DEVICE(k, q);
     const int B = (int)q.size(0), S = (int)q.size(1), H = (int)q.size(2),
               D = (int)q.size(3);
     TORCH_CHECK(D % 2 == 0 && D <= 128, "qk_norm_rope_: D must be even, <=128");
-    TORCH_CHECK((int)k.size(1) == S && (int)k.size(2) == H, "k shape mismatch");
+    TORCH_CHECK(k.sizes() == q.sizes(), "qk_norm_rope_: k ", k.sizes(),
+                " must have q's shape ", q.sizes());
+    check_norm_weight("qk_norm_rope_", "wq", wq, D, q);
+    check_norm_weight("qk_norm_rope_", "wk", wk, D, q);
+    check_cs_table("qk_norm_rope_", cs, S, D, q);
+    const long rows = (long)B * S * H;
+    if (rows == 0 || D == 0) return;
+    TORCH_CHECK(q.stride(3) == 1 && k.stride(3) == 1,
+                "qk_norm_rope_: last dim contiguous");
     auto csf = cs.to(at::kFloat).contiguous();
-    TORCH_CHECK((int)csf.size(0) == S && (int)csf.size(1) == D / 2, "cs shape");
     auto wqc = wq.contiguous();
     auto wkc = wk.contiguous();
-    const long rows = (long)B * S * H;
     const long blocks = (((rows + 3) / 4) * 64 + 255) / 256;
     PA_WITH_ELEM16(q.scalar_type(), hipLaunchKernelGGL(
         qk_norm_rope_kernel<E>, dim3((unsigned)blocks), dim3(256), 0,
@@ -201,23 +228,35 @@ std::vector<at::Tensor> pack_joint_qkv(at::Tensor txt_qkv, at::Tensor img_qkv,
                 "pack_joint_qkv: bf16 or fp16 only, got ",
                 txt_qkv.scalar_type());
     CHECK_SAME_DTYPE(img_qkv, txt_qkv);
-    CHECK_SAME_DTYPE(wq_t, txt_qkv);
-    CHECK_SAME_DTYPE(wk_t, txt_qkv);
-    CHECK_SAME_DTYPE(wq_i, txt_qkv);
-    CHECK_SAME_DTYPE(wk_i, txt_qkv);
+    CHECK_SAME_DEVICE(img_qkv, txt_qkv);
     const int B = (int)txt_qkv.size(0), T = (int)txt_qkv.size(1),
               H = (int)txt_qkv.size(3), D = (int)txt_qkv.size(4);
     const int Si = (int)img_qkv.size(1);
-    TORCH_CHECK(txt_qkv.stride(4) == 1 && img_qkv.stride(4) == 1,
-                "last dim contiguous");
-    TORCH_CHECK(D % 2 == 0 && D <= 128, "D must be even and <= 128");
+    TORCH_CHECK(D % 2 == 0 && D <= 128,
+                "pack_joint_qkv: D must be even and <= 128");
+    // one set of B, H, D indexes both streams and the joint output
+    TORCH_CHECK(txt_qkv.size(2) == 3 && img_qkv.size(2) == 3 &&
+                img_qkv.size(0) == B && img_qkv.size(3) == H &&
+                img_qkv.size(4) == D,
+                "pack_joint_qkv: txt [B,T,3,H,D] and img [B,Si,3,H,D] must "
+                "share B, H and D, got txt ", txt_qkv.sizes(), ", img ",
+                img_qkv.sizes());
+    check_norm_weight("pack_joint_qkv", "wq_t", wq_t, D, txt_qkv);
+    check_norm_weight("pack_joint_qkv", "wk_t", wk_t, D, txt_qkv);
+    check_norm_weight("pack_joint_qkv", "wq_i", wq_i, D, txt_qkv);
+    check_norm_weight("pack_joint_qkv", "wk_i", wk_i, D, txt_qkv);
+    check_cs_table("pack_joint_qkv", cs, (long)T + Si, D, txt_qkv);
+    TORCH_CHECK(txt_qkv.numel() == 0 || txt_qkv.stride(4) == 1,
+                "pack_joint_qkv: txt last dim contiguous");
+    TORCH_CHECK(img_qkv.numel() == 0 || img_qkv.stride(4) == 1,
+                "pack_joint_qkv: img last dim contiguous");
     auto csf = cs.to(at::kFloat).contiguous();
-    TORCH_CHECK((int)csf.size(0) == T + Si, "cs must cover the joint sequence");
     auto opts = txt_qkv.options();
     auto oq = at::empty({B, T + Si, H, D}, opts);
     auto ok = at::empty({B, T + Si, H, D}, opts);
     auto ov = at::empty({B, T + Si, H, D}, opts);
     const long rows = (long)B * (T + Si) * H;
+    if (rows == 0 || D == 0) return {oq, ok, ov};
     const long blocks = (((rows + 3) / 4) * 64 + 255) / 256;
     auto wqtc = wq_t.contiguous(), wktc = wk_t.contiguous();
     auto wqic = wq_i.contiguous(), wkic = wk_i.contiguous();

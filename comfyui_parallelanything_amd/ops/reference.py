@@ -219,5 +219,5 @@ def timestep_embedding(
     args = t[:, None] * freqs[None]
     emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
     if dim % 2:
-        emb = torch.cat([emb, torch.zeros_like(emb[:, :1])], dim=-1)
+        emb = torch.cat([emb, emb.new_zeros(emb.shape[0], 1)], dim=-1)
     return emb
