@@ -465,6 +465,9 @@ def _softmax_scale(q, scale: Optional[float]) -> float:
     return scale
 
 
+_check_qkv = reference.check_qkv
+
+
 def _attn_native(q, k, v, scale: float, km, bshd: bool,
                  split: Optional[int] = None):
     """One attention call on the native kernels: (output, None), or
@@ -511,9 +514,14 @@ def attention(q, k, v, scale: Optional[float] = None,
     block_mask: optional BlockMask or raw [ceil(Sq/256), ceil(Sk/64)]
     bool/integer mask (see pack_block_mask for the contract). A raw one is
     packed per call, together with key_mask; a packed one already holds its
-    key mask, and passing key_mask= beside it raises."""
+    key mask, and passing key_mask= beside it raises.
+
+    k and v have q's batch, head count and head dim and one length Sk;
+    anything else raises ValueError (nothing is broadcast). B, H or Sq of
+    zero returns the empty result, Sk = 0 zeros: no row sees a key."""
+    Sq, Sk = _check_qkv(q, k, v, bshd=False)
     scale = _softmax_scale(q, scale)
-    km = _mask_for(key_mask, block_mask, q, q.shape[2], k.shape[2])
+    km = _mask_for(key_mask, block_mask, q, Sq, Sk)
     if q.is_cuda:
         out, why = _attn_native(q, k, v, scale, km, bshd=False)
         if out is not None:
@@ -545,8 +553,9 @@ def attention_bshd(q, k, v, scale: Optional[float] = None,
     threads) — not worth the schedule split while no headline depends on
     these shapes.
     """
+    Sq, Sk = _check_qkv(q, k, v, bshd=True)
     scale = _softmax_scale(q, scale)
-    km = _mask_for(key_mask, block_mask, q, q.shape[1], k.shape[1])
+    km = _mask_for(key_mask, block_mask, q, Sq, Sk)
     if q.is_cuda:
         out, why = _attn_native(q, k, v, scale, km, bshd=True)
         if out is not None:
@@ -565,8 +574,9 @@ def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None,
     """attention_bshd with per-stream outputs: rows [:split] and [split:]
     land in two contiguous tensors (feeds dual-stream projections with no
     reshape copies). key_mask and block_mask as in attention_bshd."""
+    Sq, Sk = _check_qkv(q, k, v, bshd=True, split=split)
     scale = _softmax_scale(q, scale)
-    km = _mask_for(key_mask, block_mask, q, q.shape[1], k.shape[1])
+    km = _mask_for(key_mask, block_mask, q, Sq, Sk)
     if q.is_cuda:
         out, why = _attn_native(q, k, v, scale, km, bshd=True, split=split)
         if out is not None:

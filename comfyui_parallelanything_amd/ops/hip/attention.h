@@ -672,36 +672,58 @@ static void launch_attn_v4(at::ScalarType st, dim3 grid, const AttnArgs& a) {
         a.mask_live, a.mask_nlive));
 }
 
-// The one attention launcher. split > 0 (bshd only) writes rows >= split to
-// a second tensor; km != nullptr selects the MASKED instantiations, and a
-// 3-D km->live their QLIST flavour.
+// The one attention launcher. has_split (bshd only) writes rows >= split to
+// a second tensor, 0 < split < S; km != nullptr selects the MASKED
+// instantiations, and a 3-D km->live their QLIST flavour.
 static std::vector<at::Tensor> attn_fwd_launch(
     at::Tensor q, at::Tensor k, at::Tensor v, double scale, bool bshd,
-    long split, const AttnKeyMask* km) {
+    bool has_split, long split, const AttnKeyMask* km) {
     CHECK_GPU(q);
     TORCH_CHECK(is_elem16(q.scalar_type()),
                 "attn_fwd: bf16 or fp16 only, got ", q.scalar_type());
     CHECK_SAME_DTYPE(k, q);
     CHECK_SAME_DTYPE(v, q);
-    TORCH_CHECK(q.dim() == 4, "attn_fwd expects 4-D q/k/v");
+    CHECK_SAME_DEVICE(k, q);
+    CHECK_SAME_DEVICE(v, q);
+    TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
+                "attn_fwd expects 4-D q/k/v");
     // layouts: bshd = [B, S, H, D] (strided views allowed),
     //          else  = [B, H, S, D] (must be row-contiguous per head)
     const int b_ax = 0, s_ax = bshd ? 1 : 2, h_ax = bshd ? 2 : 1, d_ax = 3;
     const int B = (int)q.size(b_ax), S = (int)q.size(s_ax),
               H = (int)q.size(h_ax), D = (int)q.size(d_ax);
     TORCH_CHECK(D == 64 || D == 128, "attn_fwd: D must be 64 or 128");
+    // The kernel indexes k and v with q's batch, head and dim counts: a k
+    // or v with fewer of any is read past its end, never broadcast.
+    TORCH_CHECK(k.size(b_ax) == B && v.size(b_ax) == B,
+                "attn_fwd: k/v batch must equal q's batch (", B, "), got k ",
+                k.size(b_ax), ", v ", v.size(b_ax));
+    TORCH_CHECK(k.size(h_ax) == H && v.size(h_ax) == H,
+                "attn_fwd: k/v heads must equal q's heads (", H, "), got k ",
+                k.size(h_ax), ", v ", v.size(h_ax));
+    TORCH_CHECK(k.size(d_ax) == D && v.size(d_ax) == D,
+                "attn_fwd: k/v head dim must equal q's head dim (", D,
+                "), got k ", k.size(d_ax), ", v ", v.size(d_ax));
+    TORCH_CHECK(v.size(s_ax) == k.size(s_ax),
+                "attn_fwd: v must have k's length (", k.size(s_ax),
+                " keys), got ", v.size(s_ax));
+    TORCH_CHECK(!has_split || (split > 0 && split < S),
+                "attn_fwd: split must lie inside (0, S = ", S, "), got ",
+                split);
+    // The kernel's 16-byte vector loads need every stride a multiple of 8
+    // elements and a 16-byte aligned base; anything else is copied once.
     auto fix = [&](at::Tensor t) {
         if (t.stride(d_ax) != 1 || (t.stride(s_ax) % 8) != 0 ||
-            (t.stride(h_ax) % 8) != 0)
+            (t.stride(h_ax) % 8) != 0 || (t.stride(b_ax) % 8) != 0)
             t = t.contiguous();
+        if ((reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) != 0)
+            t = t.clone(at::MemoryFormat::Contiguous);
         return t;
     };
     auto qc = fix(q);
     auto kc = fix(k);
     auto vc = fix(v);
     const int Sk = (int)kc.size(s_ax);
-    TORCH_CHECK((int)vc.size(s_ax) == Sk && (int)kc.size(h_ax) == H,
-                "attn: k/v shape mismatch");
     if (km != nullptr) {
         const long n_tiles = (Sk + 63) / 64;
         TORCH_CHECK(km->words.device() == qc.device() &&
@@ -735,12 +757,22 @@ static std::vector<at::Tensor> attn_fwd_launch(
                         km->nlive.is_contiguous(),
                     "attn_fwd: key mask tensors must be contiguous");
     }
-    const bool do_split = split > 0 && split < S && bshd;
+    const bool do_split = has_split && bshd;
     at::Tensor out = bshd
         ? at::empty({B, do_split ? (int)split : S, H, D}, qc.options())
         : at::empty({B, H, S, D}, qc.options());
     at::Tensor out2;
     if (do_split) out2 = at::empty({B, S - (int)split, H, D}, qc.options());
+    // Nothing to compute: an empty result (a grid of zero blocks is a launch
+    // error), or zeros where no row sees a key.
+    if (B == 0 || H == 0 || S == 0 || Sk == 0) {
+        out.zero_();
+        if (do_split) {
+            out2.zero_();
+            return {out, out2};
+        }
+        return {out};
+    }
     const long BH = (long)B * H;
     const unsigned nq = (unsigned)((S + 255) / 256);
     // 1-D XCD-affine grid: same-(b,h) q-tiles share an XCD's L2
@@ -777,36 +809,41 @@ static std::vector<at::Tensor> attn_fwd_launch(
 }
 
 at::Tensor attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, double scale) {
-    return attn_fwd_launch(q, k, v, scale, /*bshd=*/false, -1, nullptr)[0];
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/false, false, 0,
+                           nullptr)[0];
 }
 
 at::Tensor attn_fwd_bshd(at::Tensor q, at::Tensor k, at::Tensor v, double scale) {
-    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, -1, nullptr)[0];
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, false, 0,
+                           nullptr)[0];
 }
 
 std::vector<at::Tensor> attn_fwd_bshd_split(at::Tensor q, at::Tensor k,
                                             at::Tensor v, double scale,
                                             long split) {
-    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, split, nullptr);
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, true, split,
+                           nullptr);
 }
 
 at::Tensor attn_fwd_masked(at::Tensor q, at::Tensor k, at::Tensor v,
                            double scale, at::Tensor words, at::Tensor live,
                            at::Tensor nlive) {
     const AttnKeyMask km{words, live, nlive};
-    return attn_fwd_launch(q, k, v, scale, /*bshd=*/false, -1, &km)[0];
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/false, false, 0,
+                           &km)[0];
 }
 
 at::Tensor attn_fwd_bshd_masked(at::Tensor q, at::Tensor k, at::Tensor v,
                                 double scale, at::Tensor words,
                                 at::Tensor live, at::Tensor nlive) {
     const AttnKeyMask km{words, live, nlive};
-    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, -1, &km)[0];
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, false, 0,
+                           &km)[0];
 }
 
 std::vector<at::Tensor> attn_fwd_bshd_split_masked(
     at::Tensor q, at::Tensor k, at::Tensor v, double scale, long split,
     at::Tensor words, at::Tensor live, at::Tensor nlive) {
     const AttnKeyMask km{words, live, nlive};
-    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, split, &km);
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, true, split, &km);
 }

@@ -141,6 +141,31 @@ def as_bool_block_mask(mask: torch.Tensor, Sq: int, Sk: int) -> torch.Tensor:
     return mask if mask.dtype == torch.bool else mask != 0
 
 
+def check_qkv(q, k, v, bshd: bool = False, split: Optional[int] = None):
+    """k and v must have q's batch, head count and head dim, and one length
+    between them; ``split`` lies inside (0, Sq). The native kernel indexes k
+    and v with q's counts and would read past a smaller tensor, so nothing
+    is broadcast, on any device, and the refusal comes before any mask is
+    packed. Returns (Sq, Sk)."""
+    if not (q.dim() == 4 and k.dim() == 4 and v.dim() == 4):
+        raise ValueError(f"attention expects 4-D q/k/v, got {q.dim()}-D, "
+                         f"{k.dim()}-D, {v.dim()}-D")
+    s_ax, h_ax = (1, 2) if bshd else (2, 1)
+    for name, ax in (("batch", 0), ("heads", h_ax), ("head dim", 3)):
+        if not k.shape[ax] == v.shape[ax] == q.shape[ax]:
+            raise ValueError(
+                f"attention: k/v {name} must equal q's {name} "
+                f"({q.shape[ax]}), got k {k.shape[ax]}, v {v.shape[ax]}")
+    Sq, Sk = q.shape[s_ax], k.shape[s_ax]
+    if v.shape[s_ax] != Sk:
+        raise ValueError(f"attention: v must have k's length ({Sk} keys), "
+                         f"got {v.shape[s_ax]}")
+    if split is not None and not 0 < int(split) < Sq:
+        raise ValueError(f"attention: split must lie inside (0, S = {Sq}), "
+                         f"got {split}")
+    return Sq, Sk
+
+
 def attention(
     q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None,
     key_mask: Optional[torch.Tensor] = None,
@@ -160,7 +185,11 @@ def attention(
     rows at keys no query row of that batch element sees are don't-care
     (zeroed before the matmuls), and a query row with no visible key gives
     zeros.
+
+    k and v have q's batch, head count and head dim (ValueError otherwise:
+    nothing is broadcast, as on the native kernels). Sk = 0 gives zeros.
     """
+    check_qkv(q, k, v)
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     dtype = q.dtype

@@ -131,7 +131,8 @@ def test_float_masks_raise(qkv, dtype):
     with pytest.raises(ValueError, match="additive"):
         R.attention(q, k, v, key_mask=m)
     with pytest.raises(ValueError, match="additive"):
-        ops.attention_bshd(q, k, v, key_mask=m)
+        ops.attention_bshd(*(t.permute(0, 2, 1, 3) for t in (q, k, v)),
+                           key_mask=m)
 
 
 def test_mask_shape_mismatch_raises(qkv):
