@@ -55,12 +55,16 @@ class WanBlock(nn.Module):
         self.cross_proj = nn.Linear(dim, dim)
         self.ffn = FusedMLP(dim, ffn_dim, dim)
 
-    def forward(self, x, e, context, pe, key_mask=None, block_mask=None):
+    def forward(self, x, e, context, pe, key_mask=None, block_mask=None,
+                self_attn=None):
         # e: [B, 6, dim] time-modulation; learned bias added per block
         # key_mask: optional ops.KeyMask over the context tokens — masks the
         # cross-attention only
         # block_mask: optional ops.BlockMask over the space-time tokens —
         # sparsifies the self-attention only (WanConfig.self_attn_frame_window)
+        # self_attn: optional (q, k, v, scale) -> [B,S,H,D] in place of the
+        # local self-attention: x is a token shard and the keys live on other
+        # ranks (parallel.sequence)
         m = (e + self.mod).unbind(dim=1)  # 6 x [B, dim]
         shift1, scale1, gate1, shift2, scale2, gate2 = m
 
@@ -72,8 +76,12 @@ class WanBlock(nn.Module):
             q, k, self.self_norm.query_norm.scale,
             self.self_norm.key_norm.scale, pe,
         )
-        attn = ops.attention_bshd(q, k, v, self.scale,
-                                  block_mask=block_mask).flatten(2)
+        if self_attn is None:
+            attn = ops.attention_bshd(q, k, v, self.scale,
+                                      block_mask=block_mask)
+        else:
+            attn = self_attn(q, k, v, self.scale)
+        attn = attn.flatten(2)
         x = ops.gate_residual(x, gate1, self.self_proj(attn))
 
         h = self.norm_cross(x)
@@ -163,6 +171,9 @@ class WanDiT(nn.Module):
         self.head = nn.Linear(cfg.dim, self.patch_dim)
         self._pe_cache: dict = {}
         self._mask_cache: dict = {}  # packed frame-window BlockMasks
+        # set by parallel.sequence.install_sequence_parallel; None = every
+        # token on this device
+        self._seq_parallel = None
 
     def _frame_window_mask(self, B, f, tokens_per_frame, device):
         """The packed self-attention BlockMask, or None for dense attention.
@@ -198,6 +209,14 @@ class WanDiT(nn.Module):
     def forward(self, x, timesteps, context=None, image_cond=None,
                 attention_mask=None, **kwargs):
         cfg = self.cfg
+        sp = self._seq_parallel
+        if sp is not None:
+            if cfg.self_attn_frame_window is not None:
+                raise ValueError(
+                    "self_attn_frame_window with sequence parallelism is "
+                    "not supported: the ring has no block masks")
+            x, timesteps, context, image_cond, attention_mask = sp.broadcast(
+                x, timesteps, context, image_cond, attention_mask)
         B, C, F, H, W = x.shape
         pf, ph, pw = cfg.patch_size
         f, h, w = F // pf, H // ph, W // pw
@@ -224,13 +243,16 @@ class WanDiT(nn.Module):
             .permute(0, 2, 4, 6, 1, 3, 5, 7)
             .reshape(B, f * h * w, self.patch_dim_in)
         )
+        pe = self._pe(f, h, w, x.device)
+        if sp is not None:
+            # this rank's token shard, and its rows of the RoPE table
+            tokens, pe = sp.shard(tokens, pe)
         seq = self.patch_in(tokens)
         if context is None:
             context = torch.zeros(B, 1, cfg.ctx_dim, device=x.device, dtype=x.dtype)
         ctx = self.txt_in(context)
         tvec = self.time_in.forward_timestep(timesteps)
         e = self.time_proj(torch.nn.functional.silu(tvec)).view(B, 6, cfg.dim)
-        pe = self._pe(f, h, w, x.device)
         mk = {}
         if attention_mask is not None:
             # packed once per forward, shared by every block's cross-attention
@@ -238,10 +260,14 @@ class WanDiT(nn.Module):
         bm = self._frame_window_mask(B, f, h * w, x.device)
         if bm is not None:
             mk["block_mask"] = bm
+        if sp is not None:
+            mk["self_attn"] = sp.attention
         for block in self.transformer_blocks:
             seq = block(seq, e, ctx, pe, **mk)
         shift, scale = self.head_mod(torch.nn.functional.silu(tvec)).chunk(2, dim=-1)
         out = self.head(ops.layer_norm_mod(seq, scale, shift))
+        if sp is not None:
+            out = sp.gather(out)    # every rank holds every token's output
         return (
             out.view(B, f, h, w, C, pf, ph, pw)
             .permute(0, 4, 1, 5, 2, 6, 3, 7)

@@ -598,6 +598,121 @@ def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None,
     return out[:, :split].contiguous(), out[:, split:].contiguous()
 
 
+_NO_BLOCK_LSE = ("block masks are not supported together with the "
+                 "log-sum-exp output (attention_lse / attention_bshd_lse take "
+                 "key_mask= only)")
+
+
+def _attn_lse_native(q, k, v, scale: float, km, bshd: bool):
+    """_attn_native for the LSE entry points ext.attn_fwd[_bshd]_lse[_masked]:
+    ((out, lse), None) or (None, why). The D < 128 zero-pad route is the
+    plain BSHD op's: padding q and k leaves every score, so the lse,
+    unchanged."""
+    name = ("attn_fwd" + ("_bshd" if bshd else "") + "_lse"
+            + ("_masked" if km is not None else ""))
+    ext = _require_ext(name)
+    if ext is None:
+        return None, None
+    fn = getattr(ext, name)
+    args = (float(scale),)
+    if km is not None:
+        args += (km.words, km.live, km.nlive)
+    D = q.shape[-1]
+    if q.dtype in _NATIVE16 and D in (64, 128):
+        if not bshd:
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        return tuple(fn(q, k, v, *args)), None
+    if q.dtype in _NATIVE16 and D < 128 and bshd:
+        pad = (0, (64 if D <= 64 else 128) - D)
+        out, lse = fn(*(torch.nn.functional.pad(t, pad) for t in (q, k, v)),
+                      *args)
+        return (out[..., :D], lse), None
+    return None, f"dtype={q.dtype}, D={D}"
+
+
+def attention_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
+                  block_mask=None):
+    """attention that also returns the log-sum-exp: (out [B, H, Sq, D], fp32
+    lse [B, H, Sq]), lse = log of the sum over the row's visible keys of
+    exp(scale * q.k). Partial results over disjoint key sets combine exactly
+    through it (attention_merge).
+
+    Arguments, refusals and empties as in attention; a row that sees no key
+    (Sk = 0, a batch element with no live key) has out = 0 and lse = -inf.
+    block_mask= raises ValueError: block masks with the lse are not
+    supported."""
+    if block_mask is not None:
+        raise ValueError(f"attention_lse: {_NO_BLOCK_LSE}")
+    Sq, Sk = _check_qkv(q, k, v, bshd=False)
+    scale = _softmax_scale(q, scale)
+    km = _mask_for(key_mask, None, q, Sq, Sk)
+    if q.is_cuda:
+        res, why = _attn_lse_native(q, k, v, scale, km, bshd=False)
+        if res is not None:
+            return res
+        if why is not None:
+            _unsupported("attn_fwd_lse", why)
+    return reference.attention(q, k, v, scale, return_lse=True,
+                               **_mask_kw(km))
+
+
+def attention_bshd_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
+                       block_mask=None):
+    """attention_bshd that also returns the log-sum-exp: (out [B, Sq, H, D],
+    fp32 lse [B, Sq, H]); see attention_lse. Strided views and head dims
+    under 128 work as in attention_bshd."""
+    if block_mask is not None:
+        raise ValueError(f"attention_bshd_lse: {_NO_BLOCK_LSE}")
+    Sq, Sk = _check_qkv(q, k, v, bshd=True)
+    scale = _softmax_scale(q, scale)
+    km = _mask_for(key_mask, None, q, Sq, Sk)
+    if q.is_cuda:
+        res, why = _attn_lse_native(q, k, v, scale, km, bshd=True)
+        if res is not None:
+            return res
+        if why is not None:
+            _unsupported("attn_fwd_bshd_lse", why)
+    out, lse = reference.attention(
+        q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3),
+        scale, return_lse=True, **_mask_kw(km))
+    return out.permute(0, 2, 1, 3), lse.permute(0, 2, 1).contiguous()
+
+
+ATTN_MERGE_MAX = reference.MERGE_MAX    # partials per merge: a node's GPUs
+
+
+def attention_merge(outs, lses, return_lse: bool = False):
+    """Combine N partial attention results over disjoint key sets into the
+    result over their union, exactly, through their log-sum-exp.
+
+    outs: 1 to 8 tensors [..., D] of one shape, dtype (bf16 or fp16 on the
+    GPU) and device, D a multiple of 8 there; lses: the N matching fp32
+    [...] tensors, as attention_lse / attention_bshd_lse return them. Per
+    row, in fp32: m = max_c lse_c; w_c = exp(lse_c - m); out = (sum_c w_c
+    out_c) / sum_c w_c, rounded once; lse = m + log sum_c w_c. A partial
+    with lse_c = -inf is skipped, so its out_c is don't-care (NaN included);
+    all of them -inf gives out = +0, lse = -inf. N = 1 returns the partial
+    bit for bit. Returns out, or (out, lse) with return_lse.
+
+    N outside 1..8 raises ValueError; another shape, dtype or device among
+    the partials, or an lse that is not fp32, raises RuntimeError on every
+    device."""
+    outs, lses = list(outs), list(lses)
+    reference.check_merge(outs, lses)
+    o0 = outs[0]
+    if o0.is_cuda:
+        ext = _require_ext("attn_merge")
+        if ext is not None:
+            if o0.dtype in _NATIVE16 and o0.shape[-1] % 8 == 0 \
+                    and o0.shape[-1] > 0:
+                res = ext.attn_merge([o.contiguous() for o in outs],
+                                     [l.contiguous() for l in lses],
+                                     bool(return_lse))
+                return tuple(res) if return_lse else res[0]
+            _unsupported("attn_merge", f"dtype={o0.dtype}, D={o0.shape[-1]}")
+    return reference.attention_merge(outs, lses, return_lse)
+
+
 def qk_norm_rope_(q, k, wq, wk, cs, eps: float = 1e-6):
     """In-place fused qk RMSNorm + RoPE on [B, S, H, D] views.
 

@@ -1,9 +1,10 @@
 // Fused attention forward: key-mask and block-mask packs, the v4 kernel, the
-// one launcher and the six entry points.
+// one launcher and the ten entry points.
 #pragma once
 
 using bf16x8 = short8;
 #define PA_LOG2E 1.4426950408889634f
+#define PA_LN2 0.6931471805599453f
 
 // Half-wave exchange without LDS: combine x with the partner lane's x
 // (lane i <-> lane i^32). v_permlane32_swap trades the upper half of its
@@ -221,7 +222,16 @@ std::vector<at::Tensor> pack_block_lists(at::Tensor block, at::Tensor words) {
 // batch element — row b * nq + qtile of live/nlive instead of row b. qtile
 // is block-uniform, so everything above holds unchanged; the mask words stay
 // per batch element. Nothing else differs from MASKED.
-template <int D, typename E, bool MASKED = false, bool QLIST = false>
+//
+// LSE (ring / chunked attention, see attn_merge.h): the epilogue also stores
+// the row's natural-log sum over its visible keys of exp(scale * q.k), as
+// fp32 ln2 * (m_run + log2(l_run)), and -inf for a row that saw no key
+// (l_run == 0). Both half-wave partners hold the row's m_run and l_run, so
+// the hi == 0 lane stores, through strides of its own (lse is [B, H, S] or
+// [B, S, H]). Nothing before the epilogue differs, and the instantiations
+// without the flag compile to the code they had before it existed.
+template <int D, typename E, bool MASKED = false, bool QLIST = false,
+          bool LSE = false>
 __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     const E* __restrict__ q, const E* __restrict__ k,
     const E* __restrict__ v, E* __restrict__ out,
@@ -234,7 +244,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     long o2_bs, long o2_hs, int o2_ss,
     const unsigned long long* __restrict__ mask_words = nullptr,
     const int* __restrict__ mask_live = nullptr,
-    const int* __restrict__ mask_nlive = nullptr) {
+    const int* __restrict__ mask_nlive = nullptr,
+    float* __restrict__ lse = nullptr,
+    long l_bs = 0, long l_hs = 0, long l_ss = 0) {
     using EL = Elem16<E>;
     constexpr int KVBLK = 64;
     constexpr int WAVES = 8;
@@ -612,6 +624,16 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
             oss = o_ss;
         }
         const float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;
+        if constexpr (LSE) {
+            // m_run is in the log2 domain (scale2 carries log2 e); l_run >= 1
+            // once a tile has run, since the running maximum's own key
+            // contributes exp2(0)
+            if (hi == 0)
+                lse[b * l_bs + (long)h * l_hs + (long)row * l_ss] =
+                    (l_run > 0.f)
+                        ? PA_LN2 * (m_run + __builtin_amdgcn_logf(l_run))
+                        : -__builtin_inff();
+        }
 #pragma unroll
         for (int n = 0; n < NV; ++n) {
 #pragma unroll
@@ -659,25 +681,31 @@ struct AttnArgs {
     int o2_ss;
     const unsigned long long* mask_words;
     const int *mask_live, *mask_nlive;
+    float* lse;
+    long l_bs, l_hs, l_ss;
 };
 
-template <int D, bool MASKED, bool QLIST = false>
+template <int D, bool MASKED, bool QLIST = false, bool LSE = false>
 static void launch_attn_v4(at::ScalarType st, dim3 grid, const AttnArgs& a) {
     PA_WITH_ELEM16(st, hipLaunchKernelGGL(
-        HIP_KERNEL_NAME(attn_fwd_v4_kernel<D, E, MASKED, QLIST>), grid, dim3(512), 0,
+        HIP_KERNEL_NAME(attn_fwd_v4_kernel<D, E, MASKED, QLIST, LSE>), grid,
+        dim3(512), 0,
         cur_stream(), (const E*)a.q, (const E*)a.k, (const E*)a.v, (E*)a.out,
         a.S, a.Sk, a.scale, a.H, a.q_bs, a.q_hs, a.q_ss, a.k_bs, a.k_hs,
         a.k_ss, a.v_bs, a.v_hs, a.v_ss, a.o_bs, a.o_hs, a.o_ss, a.xcd_grid,
         (E*)a.out2, a.s_split, a.o2_bs, a.o2_hs, a.o2_ss, a.mask_words,
-        a.mask_live, a.mask_nlive));
+        a.mask_live, a.mask_nlive, a.lse, a.l_bs, a.l_hs, a.l_ss));
 }
 
 // The one attention launcher. has_split (bshd only) writes rows >= split to
 // a second tensor, 0 < split < S; km != nullptr selects the MASKED
-// instantiations, and a 3-D km->live their QLIST flavour.
+// instantiations, and a 3-D km->live their QLIST flavour. want_lse appends
+// the fp32 log-sum-exp, in the output's layout without D, to the result; it
+// goes with neither a split nor a block mask.
 static std::vector<at::Tensor> attn_fwd_launch(
     at::Tensor q, at::Tensor k, at::Tensor v, double scale, bool bshd,
-    bool has_split, long split, const AttnKeyMask* km) {
+    bool has_split, long split, const AttnKeyMask* km,
+    bool want_lse = false) {
     CHECK_GPU(q);
     TORCH_CHECK(is_elem16(q.scalar_type()),
                 "attn_fwd: bf16 or fp16 only, got ", q.scalar_type());
@@ -707,6 +735,10 @@ static std::vector<at::Tensor> attn_fwd_launch(
     TORCH_CHECK(v.size(s_ax) == k.size(s_ax),
                 "attn_fwd: v must have k's length (", k.size(s_ax),
                 " keys), got ", v.size(s_ax));
+    TORCH_CHECK(!want_lse || (!has_split &&
+                              (km == nullptr || km->live.dim() != 3)),
+                "attn_fwd: the log-sum-exp output goes with neither a split "
+                "nor a block mask");
     TORCH_CHECK(!has_split || (split > 0 && split < S),
                 "attn_fwd: split must lie inside (0, S = ", S, "), got ",
                 split);
@@ -763,10 +795,18 @@ static std::vector<at::Tensor> attn_fwd_launch(
         : at::empty({B, H, S, D}, qc.options());
     at::Tensor out2;
     if (do_split) out2 = at::empty({B, S - (int)split, H, D}, qc.options());
+    at::Tensor lse;
+    if (want_lse)
+        lse = bshd ? at::empty({B, S, H}, qc.options().dtype(at::kFloat))
+                   : at::empty({B, H, S}, qc.options().dtype(at::kFloat));
     // Nothing to compute: an empty result (a grid of zero blocks is a launch
     // error), or zeros where no row sees a key.
     if (B == 0 || H == 0 || S == 0 || Sk == 0) {
         out.zero_();
+        if (want_lse) {
+            lse.fill_(-std::numeric_limits<float>::infinity());
+            return {out, lse};
+        }
         if (do_split) {
             out2.zero_();
             return {out, out2};
@@ -792,8 +832,21 @@ static std::vector<at::Tensor> attn_fwd_launch(
         do_split ? (int)out2.stride(1) : 0,
         km ? (const unsigned long long*)km->words.data_ptr() : nullptr,
         km ? km->live.data_ptr<int>() : nullptr,
-        km ? km->nlive.data_ptr<int>() : nullptr};
+        km ? km->nlive.data_ptr<int>() : nullptr,
+        want_lse ? lse.data_ptr<float>() : nullptr,
+        want_lse ? lse.stride(b_ax) : 0, want_lse ? lse.stride(h_ax) : 0,
+        want_lse ? lse.stride(s_ax) : 0};
     const at::ScalarType st = qc.scalar_type();
+    if (want_lse) {
+        if (km != nullptr) {
+            if (D == 128) launch_attn_v4<128, true, false, true>(st, grid, a);
+            else launch_attn_v4<64, true, false, true>(st, grid, a);
+        } else {
+            if (D == 128) launch_attn_v4<128, false, false, true>(st, grid, a);
+            else launch_attn_v4<64, false, false, true>(st, grid, a);
+        }
+        return {out, lse};
+    }
     if (km != nullptr && km->live.dim() == 3) {
         if (D == 128) launch_attn_v4<128, true, true>(st, grid, a);
         else launch_attn_v4<64, true, true>(st, grid, a);
@@ -846,4 +899,33 @@ std::vector<at::Tensor> attn_fwd_bshd_split_masked(
     at::Tensor words, at::Tensor live, at::Tensor nlive) {
     const AttnKeyMask km{words, live, nlive};
     return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, true, split, &km);
+}
+
+std::vector<at::Tensor> attn_fwd_lse(at::Tensor q, at::Tensor k, at::Tensor v,
+                                     double scale) {
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/false, false, 0, nullptr,
+                           /*want_lse=*/true);
+}
+
+std::vector<at::Tensor> attn_fwd_bshd_lse(at::Tensor q, at::Tensor k,
+                                          at::Tensor v, double scale) {
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, false, 0, nullptr,
+                           /*want_lse=*/true);
+}
+
+std::vector<at::Tensor> attn_fwd_lse_masked(at::Tensor q, at::Tensor k,
+                                            at::Tensor v, double scale,
+                                            at::Tensor words, at::Tensor live,
+                                            at::Tensor nlive) {
+    const AttnKeyMask km{words, live, nlive};
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/false, false, 0, &km,
+                           /*want_lse=*/true);
+}
+
+std::vector<at::Tensor> attn_fwd_bshd_lse_masked(
+    at::Tensor q, at::Tensor k, at::Tensor v, double scale, at::Tensor words,
+    at::Tensor live, at::Tensor nlive) {
+    const AttnKeyMask km{words, live, nlive};
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, false, 0, &km,
+                           /*want_lse=*/true);
 }

@@ -24,6 +24,7 @@
 #include "qk_pack.h"
 #include "fp8.h"
 #include "attention.h"
+#include "attn_merge.h"
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rms_norm", &rms_norm, "RMSNorm (gfx950)",
@@ -54,6 +55,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "attn_fwd_bshd with a packed key-padding mask");
     m.def("attn_fwd_bshd_split_masked", &attn_fwd_bshd_split_masked,
           "attn_fwd_bshd_split with a packed key-padding mask");
+    m.def("attn_fwd_lse", &attn_fwd_lse,
+          "attn_fwd returning (out, fp32 log-sum-exp [B,H,S])");
+    m.def("attn_fwd_bshd_lse", &attn_fwd_bshd_lse,
+          "attn_fwd_bshd returning (out, fp32 log-sum-exp [B,S,H])");
+    m.def("attn_fwd_lse_masked", &attn_fwd_lse_masked,
+          "attn_fwd_lse with a packed key-padding mask");
+    m.def("attn_fwd_bshd_lse_masked", &attn_fwd_bshd_lse_masked,
+          "attn_fwd_bshd_lse with a packed key-padding mask");
+    m.def("attn_merge", &attn_merge,
+          "Merge up to 8 partial attention results through their "
+          "log-sum-exp (gfx950)",
+          py::arg("outs"), py::arg("lses"), py::arg("return_lse") = false);
     m.def("gelu_tanh", &gelu_tanh, "Vectorized tanh-GELU (gfx950)");
     m.def("gelu_fp8", &gelu_fp8,
           "tanh-GELU with fused e4m3fn quant + delayed scaling (gfx950)");

@@ -170,8 +170,14 @@ def attention(
     q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None,
     key_mask: Optional[torch.Tensor] = None,
     block_mask: Optional[torch.Tensor] = None,
-) -> torch.Tensor:
+    return_lse: bool = False,
+):
     """Plain attention, [B, H, S, D] -> [B, H, S, D]. fp32 softmax.
+
+    return_lse: also return fp32 lse [B, H, Sq], the log of the sum over the
+    row's visible keys of exp(scale * q.k), and -inf on a row that sees no
+    key: (out, lse). Partial results over disjoint key sets combine exactly
+    through it (attention_merge).
 
     key_mask: optional [B, Sk] bool/integer, nonzero = attend. Masked K/V
     rows are don't-care (zeroed before the matmuls, so NaN/Inf there never
@@ -213,11 +219,13 @@ def attention(
         # a row with no visible key: softmax over all -inf is NaN -> zeros
         p = torch.where(vis.any(dim=3, keepdim=True), p,
                         torch.zeros((), device=p.device))
-        return torch.matmul(p, vf).to(dtype)
+        out = torch.matmul(p, vf).to(dtype)
+        return (out, torch.logsumexp(s, dim=-1)) if return_lse else out
     if key_mask is None:
         s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
         p = torch.softmax(s, dim=-1)
-        return torch.matmul(p, v.float()).to(dtype)
+        out = torch.matmul(p, v.float()).to(dtype)
+        return (out, torch.logsumexp(s, dim=-1)) if return_lse else out
     m = as_bool_key_mask(key_mask).to(q.device)
     if m.shape != (q.shape[0], k.shape[2]):
         raise ValueError(f"key mask {tuple(m.shape)} does not match "
@@ -231,7 +239,78 @@ def attention(
     # all keys masked: softmax over all -inf is NaN; the contract is zeros
     p = torch.where(m.any(dim=1)[:, None, None, None], p,
                     torch.zeros((), device=p.device))
-    return torch.matmul(p, vf).to(dtype)
+    out = torch.matmul(p, vf).to(dtype)
+    # logsumexp of a row of -inf is -inf (of an empty row too)
+    return (out, torch.logsumexp(s, dim=-1)) if return_lse else out
+
+
+MERGE_MAX = 8       # partials per attention_merge: the GPUs of one node
+
+
+def check_merge(outs, lses):
+    """What attention_merge takes, on every device: 1 to MERGE_MAX partials
+    (ValueError otherwise) of one shape, dtype and device, each with an fp32
+    lse of its shape without the last dim on its device (RuntimeError
+    otherwise, as from the native launcher)."""
+    n = len(outs)
+    if not 1 <= n <= MERGE_MAX:
+        raise ValueError(f"attention_merge takes 1 to {MERGE_MAX} partials "
+                         f"(one per GPU of a node), got {n}")
+    if len(lses) != n:
+        raise ValueError(f"attention_merge: {n} outs but {len(lses)} lses")
+    o0 = outs[0]
+    if o0.dim() < 1:
+        raise RuntimeError("attention_merge: partials need a last dim D")
+    for c, (o, l) in enumerate(zip(outs, lses)):
+        if o.device != o0.device or l.device != o0.device:
+            raise RuntimeError(
+                f"attention_merge: partial {c} is on {o.device} (lse on "
+                f"{l.device}), partial 0 on {o0.device}")
+        if o.dtype != o0.dtype:
+            raise RuntimeError(
+                f"attention_merge: partial {c} dtype ({o.dtype}) must match "
+                f"partial 0 ({o0.dtype})")
+        if l.dtype != torch.float32:
+            raise RuntimeError(
+                f"attention_merge: lse {c} must be fp32, got {l.dtype}")
+        if o.shape != o0.shape:
+            raise RuntimeError(
+                f"attention_merge: partial {c} has shape {list(o.shape)}, "
+                f"partial 0 {list(o0.shape)}")
+        if l.shape != o0.shape[:-1]:
+            raise RuntimeError(
+                f"attention_merge: lse {c} has shape {list(l.shape)}, its "
+                f"partial needs {list(o0.shape[:-1])}")
+
+
+def attention_merge(outs, lses, return_lse: bool = False):
+    """N partial attention results [..., D] over disjoint key sets and their
+    fp32 lse [...] -> the result over the union, in fp32 with one rounding:
+    m = max_c lse_c, w_c = exp(lse_c - m), out = (sum_c w_c out_c) / sum_c
+    w_c, lse = m + log sum_c w_c. A partial with lse_c = -inf is skipped
+    (its out_c is don't-care, NaN included); all -inf gives out = +0 and
+    lse = -inf. N = 1 returns the partial bit for bit."""
+    check_merge(outs, lses)
+    dtype = outs[0].dtype
+    L = torch.stack(list(lses))                         # [N, ...]
+    m = L.amax(0)
+    dead = torch.isinf(m) & (m < 0)
+    w = torch.exp(L - torch.where(dead, torch.zeros_like(m), m))
+    live = ~(torch.isinf(L) & (L < 0))
+    w = torch.where(live, w, torch.zeros_like(w))
+    # the sum starts from -0.0, the exact identity of addition: a partial's
+    # -0.0 survives N = 1
+    acc = torch.full(outs[0].shape, -0.0, dtype=torch.float32,
+                     device=outs[0].device)
+    for c, o in enumerate(outs):
+        acc = torch.where(live[c][..., None],
+                          acc + w[c][..., None] * o.float(), acc)
+    wsum = w.sum(0)
+    out = torch.where(dead[..., None], torch.zeros_like(acc),
+                      acc / wsum.clamp_min(1e-30)[..., None]).to(dtype)
+    if not return_lse:
+        return out
+    return out, torch.where(dead, m, m + torch.log(wsum.clamp_min(1e-30)))
 
 
 def timestep_embedding(

@@ -3,3 +3,4 @@ from .engine import ParallelEngine, WorkerError, install_parallel_forward, unins
 from .cleanup import cleanup_parallel_model, register_finalizer, aggressive_cleanup  # noqa: F401
 from .pipeline import configure_pipeline, set_pipeline_mode, pipeline_mode_active  # noqa: F401
 from .replicate import replicate_module, broadcast_module  # noqa: F401
+from .sequence import install_sequence_parallel, uninstall_sequence_parallel, ring_attention_bshd  # noqa: F401

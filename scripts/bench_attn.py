@@ -21,7 +21,17 @@ H40 D128 over S = F x 3600 tokens (F = 21 gives 75 600). --block-mask
 (with the key mask, if any): full = every block live (the block-list
 kernel's overhead against --key-mask full), frame:W = the frame window of
 ops.frame_window_block_mask (needs --frames). The mask density — live
-256x64 blocks over all blocks — is printed beside each time."""
+256x64 blocks over all blocks — is printed beside each time.
+
+--shape B,H,Sq,Sk,D runs that one shape instead of the table. --lse times
+ops.attention_lse (the LSE instantiations: one more store per row) in place
+of ops.attention; it takes no block mask.
+
+--ring-chunks N prices sequence parallelism's chunking on ONE GPU, with no
+interconnect in the picture: at --shape (default B1 H40 Sq9450 Sk75600 D128,
+one of eight ranks' queries against every key of WAN 720p x 21 frames) it
+times the dense call, then N attention_lse calls over N contiguous key
+chunks plus the attention_merge, then the merge alone in GB/s."""
 import argparse
 import sys
 import time
@@ -48,6 +58,38 @@ def attn_flops(B, H, S, D, Sk=None):
     return 4.0 * B * H * S * (S if Sk is None else Sk) * D
 
 
+def ring_chunks(n, shape, dtype, dev):
+    """Dense attention against n chunk calls + merge, and the merge alone."""
+    B, H, S, Sk, D = shape
+    print(f"== ring chunks: B{B} H{H} Sq{S} Sk{Sk} D{D}, {n} chunks "
+          f"({dtype}, random data) ==")
+    q = torch.randn(B, H, S, D, device=dev, dtype=dtype)
+    k = torch.randn(B, H, Sk, D, device=dev, dtype=dtype)
+    v = torch.randn_like(k)
+    # each chunk a buffer of its own, as it arrives from the ring
+    cuts = [Sk // n + (1 if c < Sk % n else 0) for c in range(n)]
+    ks = [t.contiguous() for t in k.split(cuts, dim=2)]
+    vs = [t.contiguous() for t in v.split(cuts, dim=2)]
+
+    def chunked():
+        parts = [ops.attention_lse(q, kc, vc) for kc, vc in zip(ks, vs)]
+        return ops.attention_merge([p[0] for p in parts],
+                                   [p[1] for p in parts])
+
+    parts = [ops.attention_lse(q, kc, vc) for kc, vc in zip(ks, vs)]
+    outs, lses = [p[0] for p in parts], [p[1] for p in parts]
+    dense = timeit(lambda: ops.attention(q, k, v), iters=10)
+    split = timeit(chunked, iters=10)
+    merge = timeit(lambda: ops.attention_merge(outs, lses), iters=20)
+    nbytes = (n + 1) * outs[0].numel() * 2 + n * lses[0].numel() * 4
+    tf = attn_flops(B, H, S, D, Sk) / 1e12
+    print(f"  dense:            {dense*1e3:8.3f} ms  {tf/dense:7.1f} TF/s")
+    print(f"  {n} chunks + merge: {split*1e3:8.3f} ms  {tf/split:7.1f} TF/s  "
+          f"({split/dense:.4f} of dense)")
+    print(f"  merge alone:      {merge*1e3:8.3f} ms  "
+          f"{nbytes/merge/1e9:7.0f} GB/s ({nbytes/1e6:.1f} MB)")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16")
@@ -60,7 +102,18 @@ def main():
     ap.add_argument("--frames", type=int, default=0,
                     help="run the WAN 720p shape with this many latent "
                          "frames (3600 tokens each) instead of the table")
+    ap.add_argument("--shape", default="", metavar="B,H,Sq,Sk,D")
+    ap.add_argument("--lse", action="store_true",
+                    help="time ops.attention_lse instead of ops.attention")
+    ap.add_argument("--ring-chunks", type=int, default=0, metavar="N")
     args = ap.parse_args()
+    shape = None
+    if args.shape:
+        shape = tuple(int(x) for x in args.shape.split(","))
+        if len(shape) != 5:
+            ap.error("--shape takes B,H,Sq,Sk,D")
+    if args.lse and args.block_mask != "none":
+        ap.error("--lse takes no block mask")
     window = None
     if args.block_mask.startswith("frame:"):
         window = int(args.block_mask.split(":", 1)[1])
@@ -71,13 +124,20 @@ def main():
     dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
     assert torch.cuda.is_available()
     dev = "cuda"
-    print(f"== attention ({args.dtype}, random data, "
+    if args.ring_chunks:
+        ring_chunks(args.ring_chunks, shape or (1, 40, 9450, 75600, 128),
+                    dtype, dev)
+        return
+    attn = ops.attention_lse if args.lse else ops.attention
+    print(f"== attention{' + lse' if args.lse else ''} ({args.dtype}, random data, "
           f"key mask: {args.key_mask}, block mask: {args.block_mask}) ==")
     tokens_per_frame = 3600  # 720p: (720/16) x (1280/16) latent patches
     video = {f"wan720p_f{args.frames}": (
         1, 40, args.frames * tokens_per_frame,
         args.frames * tokens_per_frame, 128)}
-    for name, (B, H, S, Sk, D) in (video if args.frames > 0 else {
+    if shape is not None:
+        video = {"shape": shape}
+    for name, (B, H, S, Sk, D) in (video if args.frames > 0 or shape else {
         "flux_b8": (8, 24, 4608, 4608, 128),
         "flux_b1": (1, 24, 4608, 4608, 128),
         "sdxl_mid": (4, 20, 1024, 1024, 64),
@@ -102,7 +162,7 @@ def main():
                          args.frames, tokens_per_frame, window, device=dev))
             mk = {"block_mask": ops.pack_block_mask(block, B, S, Sk, km)}
             note = f"  density {block.float().mean().item():.4f}"
-        dt = timeit(lambda: ops.attention(q, k, v, **mk), iters=10)
+        dt = timeit(lambda: attn(q, k, v, **mk), iters=10)
         tf = attn_flops(B, H, S, D, Sk) / dt / 1e12
         print(f"  {name:10s} B{B} H{H} S{S} Sk{Sk} D{D}: {dt*1e3:8.2f} ms  "
               f"{tf:7.1f} TF/s{note}")
