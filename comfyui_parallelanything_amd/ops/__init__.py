@@ -729,9 +729,11 @@ def qk_norm_rope_(q, k, wq, wk, cs, eps: float = 1e-6):
     # fp32 throughout, one rounding at the end, as the kernel does: rounding
     # the normalised row to 16 bits first costs whole spacings wherever the
     # rotation cancels
-    cs = cs.float()
-    qn = reference.rms_norm(q.float(), wq.float(), eps).permute(0, 2, 1, 3)
-    kn = reference.rms_norm(k.float(), wk.float(), eps).permute(0, 2, 1, 3)
+    # (fp64 views stay fp64: reference._wide)
+    wide = reference._wide
+    cs = wide(cs)
+    qn = reference.rms_norm(wide(q), wide(wq), eps).permute(0, 2, 1, 3)
+    kn = reference.rms_norm(wide(k), wide(wk), eps).permute(0, 2, 1, 3)
     q.copy_(reference.rope_apply(qn, cs).permute(0, 2, 1, 3))
     k.copy_(reference.rope_apply(kn, cs).permute(0, 2, 1, 3))
     return q, k

@@ -14,14 +14,21 @@ import torch
 import torch.nn.functional as F
 
 
+def _wide(x: torch.Tensor) -> torch.Tensor:
+    """The dtype a reference op computes in: fp32, and fp64 for an fp64
+    input, so a module cast with .double() is an fp64 reference end to end
+    (tests/block_cases.py) instead of an fp32 one stored in fp64."""
+    return x if x.dtype == torch.float64 else x.float()
+
+
 def rms_norm(x: torch.Tensor, weight: Optional[torch.Tensor], eps: float = 1e-6) -> torch.Tensor:
     """RMSNorm over the last dim (FLUX qk-norm and single-stream norms)."""
     dtype = x.dtype
-    xf = x.float()
+    xf = _wide(x)
     rrms = torch.rsqrt(xf.pow(2).mean(dim=-1, keepdim=True) + eps)
     out = xf * rrms
     if weight is not None:
-        out = out * weight.float()
+        out = out * _wide(weight)
     return out.to(dtype)
 
 
@@ -34,11 +41,11 @@ def layer_norm_mod(
     No learned affine — modulation plays that role (MMDiT convention).
     """
     dtype = x.dtype
-    out = F.layer_norm(x.float(), (x.shape[-1],), eps=eps)
+    out = F.layer_norm(_wide(x), (x.shape[-1],), eps=eps)
     if scale.dim() == x.dim() - 1:
         scale = scale.unsqueeze(1)
         shift = shift.unsqueeze(1)
-    out = out * (1.0 + scale.float()) + shift.float()
+    out = out * (1.0 + _wide(scale)) + _wide(shift)
     return out.to(dtype)
 
 
@@ -58,9 +65,9 @@ def group_norm_silu(
 ) -> torch.Tensor:
     """GroupNorm + SiLU fused (UNet ResBlock prologue)."""
     dtype = x.dtype
-    out = F.group_norm(x.float(), num_groups,
-                       weight.float() if weight is not None else None,
-                       bias.float() if bias is not None else None, eps)
+    out = F.group_norm(_wide(x), num_groups,
+                       _wide(weight) if weight is not None else None,
+                       _wide(bias) if bias is not None else None, eps)
     return F.silu(out).to(dtype)
 
 
@@ -88,7 +95,7 @@ def rope_apply(x: torch.Tensor, cs: torch.Tensor) -> torch.Tensor:
     """
     dtype = x.dtype
     B, H, S, D = x.shape
-    xf = x.float().reshape(B, H, S, D // 2, 2)
+    xf = _wide(x).reshape(B, H, S, D // 2, 2)
     if cs.dim() == 3:
         cos = cs[None, None, :, :, 0]
         sin = cs[None, None, :, :, 1]
@@ -211,9 +218,9 @@ def attention(
                                  f"[B={q.shape[0]}, Sk={Sk}]")
             vis = vis & m[:, None, None, :]             # [B, 1, Sq, Sk]
         seen = vis.any(dim=2)[..., None]                # [B|1, 1, Sk, 1]
-        kf = torch.where(seen, k.float(), torch.zeros((), device=k.device))
-        vf = torch.where(seen, v.float(), torch.zeros((), device=v.device))
-        s = torch.matmul(q.float(), kf.transpose(-1, -2)) * scale
+        kf = torch.where(seen, _wide(k), torch.zeros((), device=k.device))
+        vf = torch.where(seen, _wide(v), torch.zeros((), device=v.device))
+        s = torch.matmul(_wide(q), kf.transpose(-1, -2)) * scale
         s = s.masked_fill(~vis, float("-inf"))
         p = torch.softmax(s, dim=-1)
         # a row with no visible key: softmax over all -inf is NaN -> zeros
@@ -222,18 +229,18 @@ def attention(
         out = torch.matmul(p, vf).to(dtype)
         return (out, torch.logsumexp(s, dim=-1)) if return_lse else out
     if key_mask is None:
-        s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
+        s = torch.matmul(_wide(q), _wide(k).transpose(-1, -2)) * scale
         p = torch.softmax(s, dim=-1)
-        out = torch.matmul(p, v.float()).to(dtype)
+        out = torch.matmul(p, _wide(v)).to(dtype)
         return (out, torch.logsumexp(s, dim=-1)) if return_lse else out
     m = as_bool_key_mask(key_mask).to(q.device)
     if m.shape != (q.shape[0], k.shape[2]):
         raise ValueError(f"key mask {tuple(m.shape)} does not match "
                          f"[B={q.shape[0]}, Sk={k.shape[2]}]")
     rows = m[:, None, :, None]                      # [B, 1, Sk, 1]
-    kf = torch.where(rows, k.float(), torch.zeros((), device=k.device))
-    vf = torch.where(rows, v.float(), torch.zeros((), device=v.device))
-    s = torch.matmul(q.float(), kf.transpose(-1, -2)) * scale
+    kf = torch.where(rows, _wide(k), torch.zeros((), device=k.device))
+    vf = torch.where(rows, _wide(v), torch.zeros((), device=v.device))
+    s = torch.matmul(_wide(q), kf.transpose(-1, -2)) * scale
     s = s.masked_fill(~m[:, None, None, :], float("-inf"))
     p = torch.softmax(s, dim=-1)
     # all keys masked: softmax over all -inf is NaN; the contract is zeros
