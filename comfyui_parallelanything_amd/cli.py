@@ -55,6 +55,10 @@ def main(argv=None):
     ap.add_argument("--frame-window", type=int, default=None, metavar="N",
                     help="wan models: block-sparse self-attention over "
                          "frames within N of the query's (default: dense)")
+    ap.add_argument("--channels-last", action="store_true",
+                    help="sd15 / sdxl: keep activations and conv weights "
+                         "channels-last (NHWC GroupNorm kernels, token "
+                         "views without copies)")
     ap.add_argument("--json-out", default=None,
                     help="write the run summary as one JSON record")
     args = ap.parse_args(argv)
@@ -64,6 +68,8 @@ def main(argv=None):
             ap.error("--frame-window applies to wan models only")
         if args.frame_window < 0:
             ap.error("--frame-window must be >= 0")
+    if args.channels_last and args.model not in ("sd15", "sdxl"):
+        ap.error("--channels-last applies to sd15 and sdxl only")
     devices = args.devices.split(",")
     pcts = (
         [float(p) for p in args.percent.split(",")]
@@ -86,7 +92,8 @@ def main(argv=None):
         [make_entry(d, p) for d, p in zip(devices, pcts)]
     )
     make, make_inputs = MODELS[args.model]
-    model = make(dev=chain.lead, dtype=dtype, tiny=tiny)
+    layout = {"channels_last": True} if args.channels_last else {}
+    model = make(dev=chain.lead, dtype=dtype, tiny=tiny, **layout)
     if args.frame_window is not None:
         model.cfg.self_attn_frame_window = args.frame_window
 

@@ -6,6 +6,8 @@ network for checkpoints; shapes follow each public architecture.
 """
 from __future__ import annotations
 
+import dataclasses
+import os
 from typing import Any, Callable, Dict, Tuple
 
 import torch
@@ -78,8 +80,17 @@ def zimage_inputs(batch: int, px: int = 1024, dev="cpu", dtype=torch.bfloat16,
     return x, t, ctx, _with_text_mask({}, text_len, ctx)
 
 
-def make_sd15(dev="cpu", dtype=torch.float32, tiny=False):
+def _unet_layout(cfg: UNetConfig, channels_last: bool) -> UNetConfig:
+    """The config with channels-last on when asked for by the argument or by
+    PA_CHANNELS_LAST=1 (which lets bench.py measure the mode)."""
+    on = bool(channels_last) or os.environ.get("PA_CHANNELS_LAST", "0") == "1"
+    return dataclasses.replace(cfg, channels_last=on)
+
+
+def make_sd15(dev="cpu", dtype=torch.float32, tiny=False,
+              channels_last=False):
     cfg = UNetConfig.tiny() if tiny else UNetConfig.sd15()
+    cfg = _unet_layout(cfg, channels_last)
     torch.manual_seed(0)
     with torch.device(dev):
         m = SDUNet(cfg)
@@ -98,8 +109,10 @@ def sd15_inputs(batch: int, px: int = 256, dev="cpu", dtype=torch.float32,
     return x, t, ctx, _with_text_mask({}, text_len, ctx)
 
 
-def make_sdxl(dev="cpu", dtype=torch.bfloat16, tiny=False):
+def make_sdxl(dev="cpu", dtype=torch.bfloat16, tiny=False,
+              channels_last=False):
     cfg = UNetConfig.tiny() if tiny else UNetConfig.sdxl()
+    cfg = _unet_layout(cfg, channels_last)
     torch.manual_seed(0)
     with torch.device(dev):
         m = SDUNet(cfg)

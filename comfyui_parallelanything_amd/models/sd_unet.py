@@ -5,13 +5,19 @@ injection) and SpatialTransformer blocks (self-attn + cross-attn + GEGLU FF)
 at the configured levels. GroupNorm+SiLU and attention route through the
 ops dispatch (gfx950 HIP kernels on GPU); convs go through MIOpen via torch.
 
+UNetConfig.channels_last (opt-in) keeps every activation channels-last from
+the input conv to the output conv: the norms run ops.group_norm, the
+ResBlock's timestep projection enters its second norm as channel_add, and
+the SpatialTransformer takes its tokens as a view. The module tree and the
+parameter names are the same in both modes.
+
 Forward contract: forward(x, timesteps, context=None, y=None) — matches the
 engine intercept signature (reference any_device_parallel.py:1287).
 """
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import List, Optional, Tuple
 
 import torch
@@ -27,8 +33,15 @@ class GNSiLU(nn.Module):
         self.groups = min(groups, channels)
         self.weight = nn.Parameter(torch.ones(channels))
         self.bias = nn.Parameter(torch.zeros(channels))
+        self.channels_last = False      # set by SDUNet
 
-    def forward(self, x):
+    def forward(self, x, channel_add=None):
+        """channel_add [B, C]: normalise x + channel_add[:, :, None, None]
+        without materialising it (channels-last mode only)."""
+        if self.channels_last:
+            return ops.group_norm(x, self.groups, self.weight, self.bias,
+                                  silu=True, channel_add=channel_add)
+        assert channel_add is None
         return ops.group_norm_silu(x, self.groups, self.weight, self.bias)
 
 
@@ -41,11 +54,15 @@ class ResBlock(nn.Module):
         self.out_norm = GNSiLU(out_ch)
         self.conv2 = nn.Conv2d(out_ch, out_ch, 3, padding=1)
         self.skip = nn.Conv2d(in_ch, out_ch, 1) if in_ch != out_ch else nn.Identity()
+        self.channels_last = False      # set by SDUNet
 
     def forward(self, x, emb):
         h = self.conv1(self.in_norm(x))
-        h = h + self.emb_proj(torch.nn.functional.silu(emb))[:, :, None, None]
-        h = self.conv2(self.out_norm(h))
+        e = self.emb_proj(torch.nn.functional.silu(emb))
+        if self.channels_last:
+            h = self.conv2(self.out_norm(h, channel_add=e))
+        else:
+            h = self.conv2(self.out_norm(h + e[:, :, None, None]))
         return self.skip(x) + h
 
 
@@ -106,10 +123,18 @@ class SpatialTransformer(nn.Module):
             TransformerBlock(channels, ctx_dim, num_heads) for _ in range(depth)
         )
         self.proj_out = nn.Linear(channels, channels)
+        self.channels_last = False      # set by SDUNet
 
     def forward(self, x, context=None, key_mask=None):
         B, C, H, W = x.shape
-        h = self.norm(x).permute(0, 2, 3, 1).reshape(B, H * W, C)
+        if self.channels_last:
+            # [B, HW, C] is a view of the channels-last result, and so is
+            # the way back below
+            h = ops.group_norm(x, self.norm.num_groups, self.norm.weight,
+                               self.norm.bias, self.norm.eps)
+        else:
+            h = self.norm(x)
+        h = h.permute(0, 2, 3, 1).reshape(B, H * W, C)
         h = self.proj_in(h)
         for blk in self.blocks:
             h = blk(h, context, key_mask)
@@ -146,6 +171,7 @@ class UNetConfig:
     context_dim: int = 768
     head_dim: int = 64
     adm_in_channels: int = 0  # SDXL pooled-conditioning dim (0 = off)
+    channels_last: bool = False  # NHWC activations and conv weights
 
     @classmethod
     def sd15(cls) -> "UNetConfig":
@@ -242,6 +268,23 @@ class SDUNet(nn.Module):
 
         self.out_norm = GNSiLU(ch)
         self.out_conv = nn.Conv2d(ch, cfg.out_channels, 3, padding=1)
+        if cfg.channels_last:
+            self.to_channels_last()
+
+    def to_channels_last(self) -> "SDUNet":
+        """Switch the model to channels-last: conv weights are converted
+        once, here; the norms, ResBlocks and SpatialTransformers take their
+        channels-last paths. Parameters keep their names and shapes, so
+        checkpoints load and save as before."""
+        # a config of its own: cfg may be shared with another model
+        self.cfg = replace(self.cfg, channels_last=True)
+        for m in self.modules():
+            if isinstance(m, (GNSiLU, ResBlock, SpatialTransformer)):
+                m.channels_last = True
+            elif isinstance(m, nn.Conv2d):
+                m.weight.data = m.weight.data.contiguous(
+                    memory_format=torch.channels_last)
+        return self
 
     @torch.no_grad()
     def forward(self, x, timesteps, context=None, y=None,
@@ -262,6 +305,8 @@ class SDUNet(nn.Module):
         # everywhere
         km = None if attention_mask is None else \
             context_key_mask(attention_mask, context)
+        if cfg.channels_last:
+            x = x.contiguous(memory_format=torch.channels_last)
         h = self.input_conv(x)
         skips = [h]
         for mod in self.down:
@@ -271,4 +316,6 @@ class SDUNet(nn.Module):
         for mod in self.up:
             h = torch.cat([h, skips.pop()], dim=1)
             h = mod(h, emb, context, km)
-        return self.out_conv(self.out_norm(h))
+        h = self.out_conv(self.out_norm(h))
+        # a plain NCHW result in both modes
+        return h.contiguous() if cfg.channels_last else h

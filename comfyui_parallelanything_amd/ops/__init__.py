@@ -227,6 +227,61 @@ def group_norm_silu(x, num_groups: int, weight=None, bias=None,
     return reference.group_norm_silu(x, num_groups, weight, bias, eps)
 
 
+# Limits of the channels-last GroupNorm kernels (ops/hip/group_norm_nhwc.h)
+_GN_NHWC_MAX_C = 4096
+_GN_NHWC_MAX_GROUPS = 256
+
+
+def _gn_nhwc_gap(x, num_groups, tensors) -> Optional[str]:
+    """Why a GPU call is not covered by the channels-last kernels, or None."""
+    if x.dtype not in _NATIVE16:
+        return f"dtype={x.dtype}"
+    if not x.is_contiguous(memory_format=torch.channels_last):
+        return "not dense channels-last"
+    C = x.shape[1]
+    if C % 8 != 0 or C > _GN_NHWC_MAX_C or num_groups > _GN_NHWC_MAX_GROUPS:
+        return f"C={C}, groups={num_groups}"
+    if x.data_ptr() % 16 or any(
+            t is not None and (not t.is_contiguous() or t.data_ptr() % 16)
+            for t in tensors):
+        return "strided or unaligned operand"
+    return None
+
+
+def group_norm(x, num_groups: int, weight=None, bias=None, eps: float = 1e-6,
+               *, silu: bool = False, channel_add=None) -> torch.Tensor:
+    """GroupNorm of x [B, C, H, W], optionally followed by SiLU, of x +
+    channel_add when a [B, C] addend is given: it is broadcast over the
+    pixels and added in fp32 before the statistics, and the unrounded sum is
+    what gets normalised. Returns x's shape, dtype and memory format.
+
+    On the GPU a 16-bit dense channels-last x with C % 8 == 0 (C <= 4096, at
+    most 256 groups) runs the channels-last kernels, and the [B, H*W, C]
+    token tensor is then a view of the result: ``y.permute(0, 2, 3,
+    1).reshape(B, H * W, C)``. Anything else there (NCHW, fp32, odd C) takes
+    the reference path with the one-time warning; NCHW models call
+    group_norm_silu.
+
+    weight and bias [C], channel_add a contiguous [B, C], all of x's dtype
+    on x's device, C a multiple of num_groups: anything else raises
+    RuntimeError on every device. B, H or W of zero returns the empty
+    result."""
+    num_groups = int(num_groups)
+    if x.is_cuda:
+        ext = _require_ext("group_norm_nhwc")
+        if ext is not None:
+            reference.check_group_norm(x, num_groups, weight, bias,
+                                       channel_add)
+            why = _gn_nhwc_gap(x, num_groups, (weight, bias, channel_add))
+            if why is None:
+                return ext.group_norm_nhwc(x, num_groups, weight, bias,
+                                           channel_add, float(eps),
+                                           bool(silu), 0)
+            _unsupported("group_norm", why)
+    return reference.group_norm(x, num_groups, weight, bias, eps, silu=silu,
+                                channel_add=channel_add)
+
+
 def rope_apply(x, cs) -> torch.Tensor:
     """Rotate adjacent pairs of x [B, H, S, D] by cs [S, D/2, 2] (cos,
     sin; any floating dtype, any strides). An odd D or another cs shape

@@ -1,7 +1,8 @@
 // MI355X (gfx950, CDNA4) native kernels for comfyui_parallelanything_amd.
 //
 // Hand-written HIP: fused attention (MFMA 32x32x16 bf16/fp16, LDS-tiled),
-// AdaLN-modulated LayerNorm, RMSNorm, GroupNorm+SiLU, RoPE apply, gated
+// AdaLN-modulated LayerNorm, RMSNorm, GroupNorm+SiLU (NCHW) and GroupNorm
+// (channels-last), RoPE apply, gated
 // residual, timestep embedding. No CUDA-compat shims, no hipify: the code
 // targets gfx950 only (wave64, 4xSIMD-32 CUs, 160 KiB LDS, per-XCD L2).
 //
@@ -20,6 +21,7 @@
 
 #include "common.h"
 #include "norm.h"
+#include "group_norm_nhwc.h"
 #include "elementwise.h"
 #include "qk_pack.h"
 #include "fp8.h"
@@ -36,6 +38,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("group_norm_silu", &group_norm_silu, "GroupNorm+SiLU (gfx950)",
           py::arg("x"), py::arg("groups"), py::arg("weight") = py::none(),
           py::arg("bias") = py::none(), py::arg("eps") = 1e-6);
+    m.def("group_norm_nhwc", &group_norm_nhwc,
+          "GroupNorm [+ SiLU] of a channels-last tensor, optional per-(b, c) "
+          "addend before the statistics (gfx950)",
+          py::arg("x"), py::arg("groups"), py::arg("weight") = py::none(),
+          py::arg("bias") = py::none(), py::arg("channel_add") = py::none(),
+          py::arg("eps") = 1e-6, py::arg("silu") = false,
+          py::arg("slab_pixels") = 0);
     m.def("rope_apply", &rope_apply, "RoPE apply (gfx950)");
     m.def("timestep_embedding", &timestep_embedding, "Sinusoidal timestep embedding");
     m.def("attn_fwd", &attn_fwd,

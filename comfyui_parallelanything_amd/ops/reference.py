@@ -71,6 +71,65 @@ def group_norm_silu(
     return F.silu(out).to(dtype)
 
 
+def check_group_norm(x, num_groups, weight, bias, channel_add):
+    """The refusals of the channels-last GroupNorm launcher, raised on every
+    device (RuntimeError) so that CPU and GPU runs take the same arguments.
+    The launcher's own limits (dense channels-last, 16-bit, C % 8 == 0) are
+    not refusals of the op: such inputs run here."""
+    def refuse_unless(ok, msg):
+        if not ok:
+            raise RuntimeError(f"group_norm: {msg}")
+
+    refuse_unless(x.dim() == 4, f"x must be [B, C, H, W], got "
+                                f"{list(x.shape)}")
+    B, C = x.shape[:2]
+    refuse_unless(int(num_groups) >= 1 and C % int(num_groups) == 0,
+                  f"C % groups != 0 (C = {C}, groups = {num_groups})")
+    for name, t, shape in (("weight", weight, (C,)), ("bias", bias, (C,)),
+                           ("channel_add", channel_add, (B, C))):
+        if t is None:
+            continue
+        refuse_unless(tuple(t.shape) == shape,
+                      f"{name} must be {list(shape)}, got {list(t.shape)}")
+        refuse_unless(t.dtype == x.dtype,
+                      f"{name} dtype ({t.dtype}) must match x ({x.dtype})")
+        refuse_unless(t.device == x.device,
+                      f"{name} is on {t.device}, x on {x.device}")
+    refuse_unless(channel_add is None or channel_add.is_contiguous(),
+                  "channel_add must be contiguous")
+
+
+def group_norm(
+    x: torch.Tensor,
+    num_groups: int,
+    weight: Optional[torch.Tensor] = None,
+    bias: Optional[torch.Tensor] = None,
+    eps: float = 1e-6,
+    *,
+    silu: bool = False,
+    channel_add: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """GroupNorm of x [B, C, H, W] with optional SiLU: GN(x + channel_add),
+    the [B, C] addend broadcast over the pixels and added in fp32 before the
+    statistics (the sum is not rounded to x's dtype). The result has x's
+    dtype and memory format: channels-last in, channels-last out."""
+    check_group_norm(x, num_groups, weight, bias, channel_add)
+    dtype = x.dtype
+    nhwc = (not x.is_contiguous()
+            and x.is_contiguous(memory_format=torch.channels_last))
+    xf = _wide(x)
+    if channel_add is not None:
+        xf = xf + _wide(channel_add)[:, :, None, None]
+    # one summation order for both memory formats
+    out = F.group_norm(xf.contiguous(), num_groups,
+                       _wide(weight) if weight is not None else None,
+                       _wide(bias) if bias is not None else None, eps)
+    if silu:
+        out = F.silu(out)
+    out = out.to(dtype)
+    return out.contiguous(memory_format=torch.channels_last) if nhwc else out
+
+
 def rope_freqs(
     positions: torch.Tensor, dim: int, theta: float = 10000.0
 ) -> torch.Tensor:
