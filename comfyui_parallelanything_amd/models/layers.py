@@ -400,10 +400,12 @@ class SingleStreamBlock(nn.Module):
             out = self.linear2_attn(attn) + self.linear2_mlp.mm_fp8(*mlp_fp8)
         elif x.is_cuda and isinstance(self.linear2_mlp, nn.Linear):
             # second GEMM accumulates into the first's output (beta=1
-            # epilogue) — no separate elementwise add
+            # epilogue) — no separate elementwise add. In place: nothing
+            # else reads acc, and the out-of-place form first copies all
+            # of it into its result
             acc = self.linear2_attn(attn).reshape(-1, hidden)
-            out = torch.addmm(
-                acc, mlp_act.reshape(-1, self.mlp_dim),
+            out = acc.addmm_(
+                mlp_act.reshape(-1, self.mlp_dim),
                 self.linear2_mlp.weight.t(),
             ).reshape(B, S, hidden)
         else:

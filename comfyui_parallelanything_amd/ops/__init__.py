@@ -180,9 +180,10 @@ def layer_norm_mod(x, scale, shift, eps: float = 1e-6) -> torch.Tensor:
         ext = _require_ext("layer_norm_mod")
         if ext is not None:
             if scale.dim() == x.dim() - 1:
-                return ext.layer_norm_mod(
-                    x.contiguous(), scale.contiguous(), shift.contiguous(), eps
-                )
+                # scale/shift go as they are: the launcher reads [B, D]
+                # rows at any row stride (column slices of the banked
+                # modulation GEMM) and copies only what it cannot read
+                return ext.layer_norm_mod(x.contiguous(), scale, shift, eps)
             _unsupported("layer_norm_mod", "per-token modulation")
     return reference.layer_norm_mod(x, scale, shift, eps)
 
@@ -206,7 +207,8 @@ def gate_residual(residual, gate, x) -> torch.Tensor:
     if x.is_cuda:
         ext = _require_ext("gate_residual")
         if ext is not None and gate.dim() == x.dim() - 1:
-            return ext.gate_residual(residual.contiguous(), gate.contiguous(),
+            # the gate goes as it is, for layer_norm_mod's reason
+            return ext.gate_residual(residual.contiguous(), gate,
                                      x.contiguous())
     return reference.gate_residual(residual, gate, x)
 

@@ -152,3 +152,15 @@ static bool is_elem16(at::ScalarType t) {
 static int grid_1d(long n) {
     return (int)std::min<long>((n + 255) / 256, 4096);
 }
+
+// A [B, D] modulation operand (scale, shift, gate) as layer_norm_mod and
+// gate_residual read it: rows of D contiguous elements, any row stride.
+// `vec` additionally asks for what a 16-byte load needs of the base and of
+// the stride. Anything else is copied dense.
+static at::Tensor mod_rows(const at::Tensor& t, bool vec) {
+    bool ok = t.dim() == 2 && (t.size(1) <= 1 || t.stride(1) == 1);
+    if (ok && vec)
+        ok = (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16) == 0 &&
+             (t.size(0) <= 1 || (t.stride(0) * t.element_size()) % 16 == 0);
+    return ok ? t : t.contiguous();
+}

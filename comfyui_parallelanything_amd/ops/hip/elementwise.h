@@ -4,28 +4,32 @@
 
 // ---------------------------------------------------------------------------
 // Gated residual: out = residual + gate[b] * x ;  x,res: [B, S, D], gate [B, D]
+// with row stride g_rs (a column slice of the banked modulation GEMM is read
+// in place).
 // ---------------------------------------------------------------------------
 template <typename T>
 __global__ void gate_residual_kernel(const T* __restrict__ res,
                                      const T* __restrict__ gate,
                                      const T* __restrict__ x,
                                      T* __restrict__ out,
-                                     long total, int S, int D) {
+                                     long total, int S, int D, long g_rs) {
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const long d = i % D;
         const long b = i / ((long)S * D);
-        out[i] = (T)((float)res[i] + (float)gate[b * D + d] * (float)x[i]);
+        out[i] = (T)((float)res[i] + (float)gate[b * g_rs + d] * (float)x[i]);
     }
 }
 
-// 16-bit fast path: 8-wide gated residual
+// 16-bit fast path: 8-wide gated residual; g_rsv is the gate's row stride in
+// 8-element vectors
 template <typename E>
 __global__ void gate_residual_vec_kernel(const E* __restrict__ res,
                                          const E* __restrict__ gate,
                                          const E* __restrict__ x,
                                          E* __restrict__ out,
-                                         long total8, int S, int DV) {
+                                         long total8, int S, int DV,
+                                         long g_rsv) {
     using EL = Elem16<E>;
     const long stride = (long)gridDim.x * blockDim.x;
     const short8* rv = reinterpret_cast<const short8*>(res);
@@ -36,7 +40,7 @@ __global__ void gate_residual_vec_kernel(const E* __restrict__ res,
          i += stride) {
         const long dv = i % DV;
         const long b = i / ((long)S * DV);
-        short8 r = rv[i], g = gv[b * DV + dv], xx = xv[i], o;
+        short8 r = rv[i], g = gv[b * g_rsv + dv], xx = xv[i], o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float f = EL::ld((unsigned short)r[j]) +
@@ -52,8 +56,8 @@ at::Tensor gate_residual(at::Tensor res, at::Tensor gate, at::Tensor x) {
     CHECK_GPU(x);
     TORCH_CHECK(x.dim() == 3 && gate.dim() == 2,
                 "gate_residual: x [B,S,D], gate [B,D]");
-    // the kernels index gate[b * D + d]: a broadcast [1, D] gate, or one of
-    // another D, would be read past its end
+    // the kernels index gate[b * row_stride + d]: a broadcast [1, D] gate,
+    // or one of another D, would be read past its end
     TORCH_CHECK(gate.size(0) == x.size(0) && gate.size(1) == x.size(2),
                 "gate_residual: gate must be [B, D] = [", x.size(0), ", ",
                 x.size(2), "], got ", gate.sizes());
@@ -65,23 +69,26 @@ at::Tensor gate_residual(at::Tensor res, at::Tensor gate, at::Tensor x) {
     CHECK_SAME_DTYPE(gate, x);
     if (x.numel() == 0) return at::empty(x.sizes(), x.options());
     auto rc = res.contiguous();
-    auto gc = gate.contiguous();
     auto xc = x.contiguous();
     auto out = at::empty_like(xc);
     const long total = xc.numel();
     const int S = (int)xc.size(1), D = (int)xc.size(2);
     const int blocks = grid_1d(total);
     const auto st = xc.scalar_type();
-    if (is_elem16(st) && (D % 8) == 0) {
+    const bool vec = is_elem16(st) && (D % 8) == 0;
+    auto gc = mod_rows(gate, vec);
+    const long g_rs = gc.stride(0);
+    if (vec) {
         PA_WITH_ELEM16(st, hipLaunchKernelGGL(
             gate_residual_vec_kernel<E>, dim3(blocks), dim3(256), 0,
             cur_stream(), (const E*)rc.data_ptr(), (const E*)gc.data_ptr(),
-            (const E*)xc.data_ptr(), (E*)out.data_ptr(), total / 8, S, D / 8));
+            (const E*)xc.data_ptr(), (E*)out.data_ptr(), total / 8, S, D / 8,
+            g_rs / 8));
     } else {
         PA_WITH_DTYPE("gate_residual", st, hipLaunchKernelGGL(
             gate_residual_kernel<T>, dim3(blocks), dim3(256), 0,
             cur_stream(), (const T*)rc.data_ptr(), (const T*)gc.data_ptr(),
-            (const T*)xc.data_ptr(), (T*)out.data_ptr(), total, S, D));
+            (const T*)xc.data_ptr(), (T*)out.data_ptr(), total, S, D, g_rs));
     }
     return out;
 }

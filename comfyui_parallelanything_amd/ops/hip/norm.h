@@ -150,19 +150,22 @@ at::Tensor rms_norm(at::Tensor x, std::optional<at::Tensor> w, double eps) {
 
 // ---------------------------------------------------------------------------
 // AdaLN-modulated LayerNorm: out = LN(x) * (1 + scale[b]) + shift[b].
-// x: [B, S, D]; scale/shift: [B, D]. One block per (b, s) row.
+// x: [B, S, D]; scale/shift: [B, D] with row strides sc_rs / sh_rs in
+// elements (column slices of one banked modulation GEMM are read in place).
+// One block per (b, s) row.
 // ---------------------------------------------------------------------------
 template <typename T>
 __global__ void layer_norm_mod_kernel(const T* __restrict__ x,
                                       const T* __restrict__ scale,
                                       const T* __restrict__ shift,
                                       T* __restrict__ out,
-                                      int S, int D, float eps) {
+                                      int S, int D, long sc_rs, long sh_rs,
+                                      float eps) {
     const long row = blockIdx.x;          // b * S + s
     const long b = row / S;
     const T* xr = x + row * (long)D;
-    const T* sc = scale + b * (long)D;
-    const T* sh = shift + b * (long)D;
+    const T* sc = scale + b * sc_rs;
+    const T* sh = shift + b * sh_rs;
     T* yr = out + row * (long)D;
     __shared__ float scratch[8];
 
@@ -284,13 +287,14 @@ __global__ void layer_norm_mod_vec_kernel(const E* __restrict__ x,
                                           const E* __restrict__ scale,
                                           const E* __restrict__ shift,
                                           E* __restrict__ out,
-                                          int S, int D, float eps) {
+                                          int S, int D, long sc_rs,
+                                          long sh_rs, float eps) {
     using EL = Elem16<E>;
     const long row = blockIdx.x;
     const long b = row / S;
     const short8* xr = reinterpret_cast<const short8*>(x + row * (long)D);
-    const short8* sc = reinterpret_cast<const short8*>(scale + b * (long)D);
-    const short8* sh = reinterpret_cast<const short8*>(shift + b * (long)D);
+    const short8* sc = reinterpret_cast<const short8*>(scale + b * sc_rs);
+    const short8* sh = reinterpret_cast<const short8*>(shift + b * sh_rs);
     short8* yr = reinterpret_cast<short8*>(out + row * (long)D);
     const int DV = D / 8;
     __shared__ float scratch[8];
@@ -311,25 +315,37 @@ at::Tensor layer_norm_mod(at::Tensor x, at::Tensor scale, at::Tensor shift,
     CHECK_GPU(x);
     TORCH_CHECK(x.dim() == 3, "layer_norm_mod expects [B, S, D]");
     auto xc = x.contiguous();
-    auto sc = scale.contiguous();
-    auto sh = shift.contiguous();
-    TORCH_CHECK(sc.sizes() == sh.sizes() && sc.dim() == 2, "scale/shift [B, D]");
+    TORCH_CHECK(scale.sizes() == shift.sizes() && scale.dim() == 2,
+                "scale/shift [B, D]");
     auto out = at::empty_like(xc);
     const int B = (int)xc.size(0), S = (int)xc.size(1), D = (int)xc.size(2);
+    // the kernels index scale[b * row_stride + d]
+    TORCH_CHECK(scale.size(0) == B && scale.size(1) == D,
+                "layer_norm_mod: scale/shift must be [B, D] = [", B, ", ", D,
+                "], got ", scale.sizes());
     dim3 grid((unsigned)((long)B * S));
     const auto st = xc.scalar_type();
     CHECK_SAME_DTYPE(scale, x);
     CHECK_SAME_DTYPE(shift, x);
-    if (is_elem16(st) && (D % 8) == 0) {
+    CHECK_SAME_DEVICE(scale, x);
+    CHECK_SAME_DEVICE(shift, x);
+    if (xc.numel() == 0) return out;
+    const bool vec = is_elem16(st) && (D % 8) == 0;
+    auto sc = mod_rows(scale, vec);
+    auto sh = mod_rows(shift, vec);
+    const long sc_rs = sc.stride(0), sh_rs = sh.stride(0);
+    if (vec) {
         PA_WITH_ELEM16(st, hipLaunchKernelGGL(
             layer_norm_mod_vec_kernel<E>, grid, dim3(256), 0, cur_stream(),
             (const E*)xc.data_ptr(), (const E*)sc.data_ptr(),
-            (const E*)sh.data_ptr(), (E*)out.data_ptr(), S, D, (float)eps));
+            (const E*)sh.data_ptr(), (E*)out.data_ptr(), S, D, sc_rs, sh_rs,
+            (float)eps));
     } else {
         PA_WITH_DTYPE("layer_norm_mod", st, hipLaunchKernelGGL(
             layer_norm_mod_kernel<T>, grid, dim3(256), 0, cur_stream(),
             (const T*)xc.data_ptr(), (const T*)sc.data_ptr(),
-            (const T*)sh.data_ptr(), (T*)out.data_ptr(), S, D, (float)eps));
+            (const T*)sh.data_ptr(), (T*)out.data_ptr(), S, D, sc_rs, sh_rs,
+            (float)eps));
     }
     return out;
 }
