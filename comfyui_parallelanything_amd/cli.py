@@ -59,6 +59,10 @@ def main(argv=None):
                     help="sd15 / sdxl: keep activations and conv weights "
                          "channels-last (NHWC GroupNorm kernels, token "
                          "views without copies)")
+    ap.add_argument("--token-ops", action="store_true",
+                    help="sd15 / sdxl: run the transformer blocks' "
+                         "LayerNorms (with the residual adds) and GEGLU on "
+                         "the native token kernels")
     ap.add_argument("--json-out", default=None,
                     help="write the run summary as one JSON record")
     args = ap.parse_args(argv)
@@ -70,6 +74,8 @@ def main(argv=None):
             ap.error("--frame-window must be >= 0")
     if args.channels_last and args.model not in ("sd15", "sdxl"):
         ap.error("--channels-last applies to sd15 and sdxl only")
+    if args.token_ops and args.model not in ("sd15", "sdxl"):
+        ap.error("--token-ops applies to sd15 and sdxl only")
     devices = args.devices.split(",")
     pcts = (
         [float(p) for p in args.percent.split(",")]
@@ -93,6 +99,8 @@ def main(argv=None):
     )
     make, make_inputs = MODELS[args.model]
     layout = {"channels_last": True} if args.channels_last else {}
+    if args.token_ops:
+        layout["token_ops"] = True
     model = make(dev=chain.lead, dtype=dtype, tiny=tiny, **layout)
     if args.frame_window is not None:
         model.cfg.self_attn_frame_window = args.frame_window

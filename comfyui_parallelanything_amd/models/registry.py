@@ -87,10 +87,16 @@ def _unet_layout(cfg: UNetConfig, channels_last: bool) -> UNetConfig:
     return dataclasses.replace(cfg, channels_last=on)
 
 
+def _unet_token_ops(cfg: UNetConfig, token_ops: bool) -> UNetConfig:
+    """Likewise for the token ops: the argument or PA_UNET_TOKEN_OPS=1."""
+    on = bool(token_ops) or os.environ.get("PA_UNET_TOKEN_OPS", "0") == "1"
+    return dataclasses.replace(cfg, token_ops=on)
+
+
 def make_sd15(dev="cpu", dtype=torch.float32, tiny=False,
-              channels_last=False):
+              channels_last=False, token_ops=False):
     cfg = UNetConfig.tiny() if tiny else UNetConfig.sd15()
-    cfg = _unet_layout(cfg, channels_last)
+    cfg = _unet_token_ops(_unet_layout(cfg, channels_last), token_ops)
     torch.manual_seed(0)
     with torch.device(dev):
         m = SDUNet(cfg)
@@ -110,9 +116,9 @@ def sd15_inputs(batch: int, px: int = 256, dev="cpu", dtype=torch.float32,
 
 
 def make_sdxl(dev="cpu", dtype=torch.bfloat16, tiny=False,
-              channels_last=False):
+              channels_last=False, token_ops=False):
     cfg = UNetConfig.tiny() if tiny else UNetConfig.sdxl()
-    cfg = _unet_layout(cfg, channels_last)
+    cfg = _unet_token_ops(_unet_layout(cfg, channels_last), token_ops)
     torch.manual_seed(0)
     with torch.device(dev):
         m = SDUNet(cfg)

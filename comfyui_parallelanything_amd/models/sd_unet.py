@@ -8,8 +8,11 @@ ops dispatch (gfx950 HIP kernels on GPU); convs go through MIOpen via torch.
 UNetConfig.channels_last (opt-in) keeps every activation channels-last from
 the input conv to the output conv: the norms run ops.group_norm, the
 ResBlock's timestep projection enters its second norm as channel_add, and
-the SpatialTransformer takes its tokens as a view. The module tree and the
-parameter names are the same in both modes.
+the SpatialTransformer takes its tokens as a view. UNetConfig.token_ops
+(opt-in, independent of the layout) runs each TransformerBlock's LayerNorms,
+two of them fused with the residual add before them, and its GEGLU through
+ops.layer_norm and ops.geglu. The module tree and the parameter names are
+the same in every mode.
 
 Forward contract: forward(x, timesteps, context=None, y=None) — matches the
 engine intercept signature (reference any_device_parallel.py:1287).
@@ -90,8 +93,11 @@ class GEGLU(nn.Module):
     def __init__(self, dim: int, inner: int):
         super().__init__()
         self.proj = nn.Linear(dim, inner * 2)
+        self.token_ops = False          # set by SDUNet
 
     def forward(self, x):
+        if self.token_ops:
+            return ops.geglu(self.proj(x))
         a, b = self.proj(x).chunk(2, dim=-1)
         return a * torch.nn.functional.gelu(b)
 
@@ -105,9 +111,20 @@ class TransformerBlock(nn.Module):
         self.attn2 = CrossAttention(dim, ctx_dim, num_heads)  # cross
         self.norm3 = nn.LayerNorm(dim)
         self.ff = nn.Sequential(GEGLU(dim, dim * 4), nn.Linear(dim * 4, dim))
+        self.token_ops = False          # set by SDUNet
 
     def forward(self, x, context=None, key_mask=None):
         # key_mask covers the context tokens: cross-attention (attn2) only
+        if self.token_ops:
+            # each residual add is fused into the norm that follows it: the
+            # op returns the new stream and its LayerNorm
+            n1, n2, n3 = self.norm1, self.norm2, self.norm3
+            h = ops.layer_norm(x, n1.weight, n1.bias, n1.eps)
+            x, h = ops.layer_norm(self.attn1(h), n2.weight, n2.bias, n2.eps,
+                                  residual=x)
+            x, h = ops.layer_norm(self.attn2(h, context, key_mask), n3.weight,
+                                  n3.bias, n3.eps, residual=x)
+            return x + self.ff(h)
         x = x + self.attn1(self.norm1(x))
         x = x + self.attn2(self.norm2(x), context, key_mask)
         x = x + self.ff(self.norm3(x))
@@ -172,6 +189,7 @@ class UNetConfig:
     head_dim: int = 64
     adm_in_channels: int = 0  # SDXL pooled-conditioning dim (0 = off)
     channels_last: bool = False  # NHWC activations and conv weights
+    token_ops: bool = False      # ops.layer_norm / ops.geglu in the blocks
 
     @classmethod
     def sd15(cls) -> "UNetConfig":
@@ -270,6 +288,8 @@ class SDUNet(nn.Module):
         self.out_conv = nn.Conv2d(ch, cfg.out_channels, 3, padding=1)
         if cfg.channels_last:
             self.to_channels_last()
+        if cfg.token_ops:
+            self.use_token_ops()
 
     def to_channels_last(self) -> "SDUNet":
         """Switch the model to channels-last: conv weights are converted
@@ -284,6 +304,16 @@ class SDUNet(nn.Module):
             elif isinstance(m, nn.Conv2d):
                 m.weight.data = m.weight.data.contiguous(
                     memory_format=torch.channels_last)
+        return self
+
+    def use_token_ops(self) -> "SDUNet":
+        """Switch every TransformerBlock to ops.layer_norm (with the fused
+        residual add) and ops.geglu. Parameters keep their names and shapes;
+        works with either layout."""
+        self.cfg = replace(self.cfg, token_ops=True)
+        for m in self.modules():
+            if isinstance(m, (TransformerBlock, GEGLU)):
+                m.token_ops = True
         return self
 
     @torch.no_grad()

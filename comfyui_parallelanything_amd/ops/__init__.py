@@ -284,6 +284,77 @@ def group_norm(x, num_groups: int, weight=None, bias=None, eps: float = 1e-6,
                                 channel_add=channel_add)
 
 
+# Limit of layer_norm_affine_kernel (ops/hip/token_ops.h): 4 vectors a lane
+_LN_AFFINE_MAX_C = 2048
+
+
+def _dense16(t: torch.Tensor) -> torch.Tensor:
+    """t as the token kernels read a dense operand: contiguous, 16-byte
+    aligned. Copies only what is neither."""
+    if not t.is_contiguous():
+        t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def layer_norm(x, weight, bias, eps: float = 1e-5, *, residual=None):
+    """Affine LayerNorm over the last dim of x [..., C]. With ``residual``
+    (x's shape) it returns (s, y): s = residual + x rounded to x's dtype, the
+    new residual stream, and y = LayerNorm(s) of that rounded s, so y is bit
+    for bit ``layer_norm(s, ...)``. Without, y alone.
+
+    On the GPU a 16-bit call with C % 8 == 0 and C <= 2048 runs the
+    one-wave-per-row kernel (fp32 arithmetic, one rounding per output);
+    anything else there (fp32, C = 5120, C % 8) takes the reference path with
+    the one-time warning. weight and bias [C] and residual of x's dtype on
+    x's device: anything else raises RuntimeError on every device. Zero rows
+    return the empty result."""
+    reference.check_layer_norm(x, weight, bias, residual)
+    if x.is_cuda:
+        ext = _require_ext("layer_norm_affine")
+        if ext is not None:
+            C = x.shape[-1]
+            if x.dtype in _NATIVE16 and C % 8 == 0 and 0 < C <= _LN_AFFINE_MAX_C:
+                res = ext.layer_norm_affine(
+                    _dense16(x).view(-1, C), _dense16(weight), _dense16(bias),
+                    None if residual is None
+                    else _dense16(residual).view(-1, C), float(eps))
+                res = [r.view(x.shape) for r in res]
+                return res[0] if residual is None else (res[0], res[1])
+            _unsupported("layer_norm", f"dtype={x.dtype}, C={C}")
+    return reference.layer_norm(x, weight, bias, eps, residual=residual)
+
+
+def geglu(y: torch.Tensor) -> torch.Tensor:
+    """GEGLU of y [..., 2N] -> [..., N]: a * gelu(g) with a = y[..., :N], g =
+    y[..., N:] and the exact erf GELU 0.5 * g * (1 + erf(g / sqrt 2)); NaN in
+    is NaN out, and 0 * inf is NaN as in the torch composition.
+
+    On the GPU a 16-bit y with N % 8 == 0 runs the kernel (fp32 arithmetic,
+    one rounding), reading in place any view whose last dim is contiguous
+    and whose leading dims collapse to rows of one 16-byte-aligned stride (a
+    column slice of a wider projection); other views are copied first.
+    fp32 or another N takes the reference path with the one-time warning. An
+    odd last dim raises RuntimeError on every device."""
+    reference.check_geglu(y)
+    if y.is_cuda:
+        ext = _require_ext("geglu")
+        if ext is not None:
+            W = y.shape[-1]
+            if W == 0:
+                return reference.geglu(y)       # empty, nothing to launch
+            if y.dtype in _NATIVE16 and W % 16 == 0:
+                try:
+                    rows = y.view(-1, W)
+                except RuntimeError:
+                    rows = None
+                if rows is None or rows.stride(1) != 1 or rows.data_ptr() % 16 \
+                        or (rows.shape[0] > 1 and rows.stride(0) % 8):
+                    rows = _dense16(y).view(-1, W)
+                return ext.geglu(rows).view(*y.shape[:-1], W // 2)
+            _unsupported("geglu", f"dtype={y.dtype}, N={W // 2}")
+    return reference.geglu(y)
+
+
 def rope_apply(x, cs) -> torch.Tensor:
     """Rotate adjacent pairs of x [B, H, S, D] by cs [S, D/2, 2] (cos,
     sin; any floating dtype, any strides). An odd D or another cs shape

@@ -2,7 +2,7 @@
 //
 // Hand-written HIP: fused attention (MFMA 32x32x16 bf16/fp16, LDS-tiled),
 // AdaLN-modulated LayerNorm, RMSNorm, GroupNorm+SiLU (NCHW) and GroupNorm
-// (channels-last), RoPE apply, gated
+// (channels-last), affine LayerNorm (+residual) and GEGLU, RoPE apply, gated
 // residual, timestep embedding. No CUDA-compat shims, no hipify: the code
 // targets gfx950 only (wave64, 4xSIMD-32 CUs, 160 KiB LDS, per-XCD L2).
 //
@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "norm.h"
+#include "token_ops.h"
 #include "group_norm_nhwc.h"
 #include "elementwise.h"
 #include "qk_pack.h"
@@ -34,6 +35,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("layer_norm_mod", &layer_norm_mod, "AdaLN-modulated LayerNorm (gfx950)");
     m.def("layer_norm_mod_fp8", &layer_norm_mod_fp8,
           "AdaLN LayerNorm with fused e4m3fn quant + delayed scaling (gfx950)");
+    m.def("layer_norm_affine", &layer_norm_affine,
+          "Affine LayerNorm of [rows, C], one wave per row; with delta also "
+          "the rounded sum x + delta, which is what it normalises (gfx950)",
+          py::arg("x"), py::arg("weight"), py::arg("bias"),
+          py::arg("delta") = py::none(), py::arg("eps") = 1e-5);
+    m.def("geglu", &geglu,
+          "GEGLU a * erf-gelu(g) of [rows, 2N] row-strided halves (gfx950)");
     m.def("gate_residual", &gate_residual, "Gated residual add (gfx950)");
     m.def("group_norm_silu", &group_norm_silu, "GroupNorm+SiLU (gfx950)",
           py::arg("x"), py::arg("groups"), py::arg("weight") = py::none(),

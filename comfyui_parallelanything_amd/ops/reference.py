@@ -130,6 +130,55 @@ def group_norm(
     return out.contiguous(memory_format=torch.channels_last) if nhwc else out
 
 
+def check_layer_norm(x, weight, bias, residual=None):
+    """What no path of ops.layer_norm accepts, raised on every device
+    (RuntimeError). The kernel's own limits (16-bit, C % 8 == 0, C <= 2048)
+    are not refusals of the op: such inputs run here."""
+    def refuse_unless(ok, msg):
+        if not ok:
+            raise RuntimeError(f"layer_norm: {msg}")
+
+    refuse_unless(x.dim() >= 1, "x must be [..., C]")
+    C = x.shape[-1]
+    named = [("weight", weight, (C,)), ("bias", bias, (C,))]
+    if residual is not None:
+        named.append(("residual", residual, tuple(x.shape)))
+    for name, t, shape in named:
+        refuse_unless(tuple(t.shape) == shape,
+                      f"{name} must be {list(shape)}, got {list(t.shape)}")
+        refuse_unless(t.dtype == x.dtype,
+                      f"{name} dtype ({t.dtype}) must match x ({x.dtype})")
+        refuse_unless(t.device == x.device,
+                      f"{name} is on {t.device}, x on {x.device}")
+
+
+def layer_norm(x, weight, bias, eps: float = 1e-5, *, residual=None):
+    """Affine LayerNorm over the last dim as nn.LayerNorm computes it, in
+    x's dtype. With ``residual``: (s, y), s = residual + x in that dtype and
+    y = LayerNorm(s): the residual add and the norm of the UNet's
+    TransformerBlock, as the block composes them in eager torch."""
+    check_layer_norm(x, weight, bias, residual)
+    if residual is None:
+        return F.layer_norm(x, (x.shape[-1],), weight, bias, eps)
+    s = residual + x
+    return s, F.layer_norm(s, (x.shape[-1],), weight, bias, eps)
+
+
+def check_geglu(y):
+    if y.dim() < 1 or y.shape[-1] % 2:
+        raise RuntimeError(f"geglu: y must be [..., 2N], got {list(y.shape)}")
+
+
+def geglu(y: torch.Tensor) -> torch.Tensor:
+    """a * gelu(g), a and g the two halves of the last dim, the erf GELU:
+    the UNet's GEGLU as the block composes it in eager torch."""
+    check_geglu(y)
+    if y.shape[-1] == 0:
+        return y.new_empty(y.shape)
+    a, g = y.chunk(2, dim=-1)
+    return a * F.gelu(g)
+
+
 def rope_freqs(
     positions: torch.Tensor, dim: int, theta: float = 10000.0
 ) -> torch.Tensor:
