@@ -604,9 +604,10 @@ def _attn_native(q, k, v, scale: float, km, bshd: bool,
 
     Picks ext.attn_fwd[_bshd][_split][_masked]; ``km`` is None, a KeyMask or
     a BlockMask, whose 3-D ``live`` selects the block-list kernels inside
-    the masked entry points. Head dims 64/128 run as they are; other 16-bit
-    head dims under 128 are zero-padded up, on the plain BSHD op only (see
-    attention_bshd)."""
+    the masked entry points. Head dims 64/128 run as they are, and so do the
+    other head dims of the extension's table (40, 80) without a split or a
+    block mask; what is left of the 16-bit head dims under 128 is zero-padded
+    up, on the plain BSHD op only (see attention_bshd)."""
     name = ("attn_fwd" + ("_bshd" if bshd else "")
             + ("_split" if split is not None else "")
             + ("_masked" if km is not None else ""))
@@ -620,7 +621,10 @@ def _attn_native(q, k, v, scale: float, km, bshd: bool,
     if km is not None:
         args += (km.words, km.live, km.nlive)
     D = q.shape[-1]
-    if q.dtype in _NATIVE16 and D in (64, 128):
+    native = D in (64, 128) or (
+        split is None and (km is None or isinstance(km, KeyMask))
+        and D in ext.attn_native_head_dims())
+    if q.dtype in _NATIVE16 and native:
         if not bshd:
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         return fn(q, k, v, *args), None
@@ -664,22 +668,28 @@ def attention_bshd(q, k, v, scale: Optional[float] = None,
     """Fused attention on [B, S, H, D] (strided views allowed — e.g. slices
     of a fused qkv projection; no transpose/contiguous copies on GPU).
 
-    Head dims that are not 64/128 but fit under them (SD1.5's 40/80) are
-    zero-padded: padding q/k leaves every softmax score unchanged, padded v
-    columns are sliced off the output.
-
     key_mask: optional KeyMask or raw [B, Sk] bool/integer mask (see
     pack_key_mask for the contract). block_mask: optional BlockMask or raw
     [ceil(Sq/256), ceil(Sk/64)] mask, as in attention.
 
-    Cost statement: the pad wastes attention FLOPs
-    proportional to Dp/D — 60% at D=40->64, 60% at D=80->128 — plus one
-    pad copy of q/k/v per call. This is acceptable because SD1.5 is the
-    PLUMBING config (BASELINE config 1 runs it on cpu,cpu); no SD-class
-    GPU performance is claimed anywhere. A native D=48/96 tile would need
-    fractional per-thread stage vectors (KVBLK*D/8 not divisible by 512
-    threads) — not worth the schedule split while no headline depends on
-    these shapes.
+    Head dims. 64 and 128 are the kernel's two tile classes. SD1.5's 40 and
+    80 have kernels of their own inside those classes (docs/KERNELS.md,
+    "Native head dims"), here and in ops.attention, plain or with key_mask=:
+    no pad, no copy, a contiguous output, and bit for bit what the zero-pad
+    route gave. Their views must start every row on 16 bytes (any slice of a
+    fused qkv projection does); one that does not raises RuntimeError.
+
+    Cost statement for what still pads. Other 16-bit head dims under 128
+    (48, 72, 88, 96, ...), and 40 / 80 with block_mask=, in
+    attention_bshd_split and in the _lse ops, are zero-padded up to 64 / 128
+    on this op: padding q/k leaves every softmax score unchanged, padded v
+    columns are sliced off the output. That wastes attention FLOPs in
+    proportion to the padded dim (60 % at 40 -> 64 and 80 -> 128) and costs
+    one pad copy each of q, k, v, and the caller's .flatten(2) copies the
+    sliced output once more. One more native head dim is one line of the
+    extension's table plus its instantiations. Head dims above 128 (160)
+    need a 256-class tile that does not exist: they take the reference path
+    with a warning.
     """
     Sq, Sk = _check_qkv(q, k, v, bshd=True)
     scale = _softmax_scale(q, scale)

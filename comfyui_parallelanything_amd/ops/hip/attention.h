@@ -26,6 +26,20 @@ PA_DEV float mul_f32_scalar(float a, float b) {
     asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+// E(a * b) as the compiled epilogue of the class kernels casts the products
+// it does not pack: fp16 from the exact product, one rounding
+// (v_fma_mixlo_f16 with a zero addend); bf16 has no such instruction and
+// rounds to fp32 first.
+template <typename E>
+PA_DEV unsigned short mul_cast_fused(float a, float b) {
+    if constexpr (std::is_same_v<E, _Float16>) {
+        unsigned int r;
+        asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(r) : "v"(a), "v"(b));
+        return (unsigned short)r;
+    } else {
+        return Elem16<E>::st(mul_f32_scalar(a, b));
+    }
+}
 
 // ---------------------------------------------------------------------------
 // Key-padding mask pack: [B, Sk] bool (nonzero = attend) -> what the MASKED
@@ -230,8 +244,19 @@ std::vector<at::Tensor> pack_block_lists(at::Tensor block, at::Tensor words) {
 // the hi == 0 lane stores, through strides of its own (lse is [B, H, S] or
 // [B, S, H]). Nothing before the epilogue differs, and the instantiations
 // without the flag compile to the code they had before it existed.
+//
+// DH (native head dims, docs/KERNELS.md "Native head dims"): the real head
+// dim, DH % 8 == 0 and DH <= D. D stays the tile class: it picks the LDS
+// row strides, the schedule and the tr addressing, so the bank analysis
+// holds for every DH. With DH < D the kernel does strictly less of the same
+// work, in the same order: ceil(DH/16) QK^T steps and ceil(DH/32) PV dim
+// tiles, K/V staged in ceil(64 * DH/8 / 512) rounds of which the last is
+// partial, and no byte at or beyond column DH of any q/k/v/out row is
+// touched. What it drops from the zero-padded class-D run are MFMA steps
+// whose operands are all zero, so the two agree bit for bit. DH == D
+// compiles to the code it had before the parameter existed.
 template <int D, typename E, bool MASKED = false, bool QLIST = false,
-          bool LSE = false>
+          bool LSE = false, int DH = D>
 __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     const E* __restrict__ q, const E* __restrict__ k,
     const E* __restrict__ v, E* __restrict__ out,
@@ -253,9 +278,15 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     constexpr int THREADS = WAVES * 64;
     constexpr int KPAD = D + 8;
     constexpr int VROW = 160;        // V row stride: 40 granules ≡ 8 mod 32
-    constexpr int KK = D / 16;        // QK^T K-steps per 32-key tile
-    constexpr int NV = D / 32;        // PV dim tiles
-    constexpr int KVECS = (KVBLK * D) / (8 * THREADS);
+    static_assert(DH % 8 == 0 && DH > 0 && DH <= D, "head dim vs tile class");
+    constexpr int KK = (DH + 15) / 16;   // QK^T K-steps per 32-key tile
+    constexpr int NV = (DH + 31) / 32;   // PV dim tiles
+    constexpr int GROW = DH / 8;         // 16-byte granules per K/V row
+    constexpr int NGRAN = KVBLK * GROW;  // granules per K/V tile
+    constexpr int KVECS = (NGRAN + THREADS - 1) / THREADS;
+    // staging round i holds a granule for every thread, or (the last round
+    // of a tile that is no multiple of 512 granules) for idx < NGRAN only
+    constexpr bool STAGE_TAIL = NGRAN % THREADS != 0;
     // D=128: double-buffered LDS (75.8 KB, still 2 blocks/CU) for the v5a
     // 1-barrier pipelined schedule; D=64 keeps the v4 2-barrier loop.
     constexpr int DBUF = (D == 128) ? 2 : 1;
@@ -305,9 +336,20 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
         const int row = q0 + l32;
         const int rr = row < S ? row : (S > 0 ? S - 1 : 0);
 #pragma unroll
-        for (int kk = 0; kk < KK; ++kk)
-            qfrag[kk] = *reinterpret_cast<const bf16x8*>(
-                qp + (long)rr * q_ss + kk * 16 + hi * 8);
+        for (int kk = 0; kk < KK; ++kk) {
+            if constexpr (DH % 16 == 0) {
+                qfrag[kk] = *reinterpret_cast<const bf16x8*>(
+                    qp + (long)rr * q_ss + kk * 16 + hi * 8);
+            } else {
+                // the last chunk's hi half starts at column DH: zeros, and
+                // no load (the bytes there belong to another head or tensor)
+                if (kk * 16 + hi * 8 < DH)
+                    qfrag[kk] = *reinterpret_cast<const bf16x8*>(
+                        qp + (long)rr * q_ss + kk * 16 + hi * 8);
+                else
+                    qfrag[kk] = bf16x8{0,0,0,0,0,0,0,0};
+            }
+        }
     }
 
     f32x16 o_acc[NV];
@@ -325,12 +367,19 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
 #pragma unroll
         for (int i = 0; i < KVECS; ++i) {
             const int idx = tid + i * THREADS;
-            const int row = idx / (D / 8);
-            const int col = (idx % (D / 8)) * 8;
+            const int row = idx / GROW;
+            const int col = (idx % GROW) * 8;
             const int src = kv0 + row;
             bool stage;
-            if constexpr (MASKED) stage = ((word >> row) & 1ull) != 0;
+            // beyond the tile's last granule row is 64 or more: the shift
+            // stays in range, and nothing is staged there whatever bit or
+            // key that row would name
+            constexpr int RMASK = STAGE_TAIL ? 63 : -1;
+            if constexpr (MASKED)
+                stage = ((word >> (row & RMASK)) & 1ull) != 0;
             else stage = src < Sk;
+            if constexpr (STAGE_TAIL)
+                if (i == KVECS - 1) stage = idx < NGRAN && stage;
             if (stage) {
                 kreg[i] = *reinterpret_cast<const bf16x8*>(kp + (long)src * k_ss + col);
                 vreg[i] = *reinterpret_cast<const bf16x8*>(vp + (long)src * v_ss + col);
@@ -344,8 +393,10 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
 #pragma unroll
         for (int i = 0; i < KVECS; ++i) {
             const int idx = tid + i * THREADS;
-            const int row = idx / (D / 8);
-            const int col = (idx % (D / 8)) * 8;
+            const int row = idx / GROW;
+            const int col = (idx % GROW) * 8;
+            if constexpr (STAGE_TAIL)
+                if (i == KVECS - 1 && idx >= NGRAN) continue;
             *reinterpret_cast<bf16x8*>(
                 &k_lds[buf * (KVBLK * KPAD) + row * KPAD + col]) = kreg[i];
         }
@@ -354,8 +405,10 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
 #pragma unroll
         for (int i = 0; i < KVECS; ++i) {
             const int idx = tid + i * THREADS;
-            const int row = idx / (D / 8);
-            const int col = (idx % (D / 8)) * 8;
+            const int row = idx / GROW;
+            const int col = (idx % GROW) * 8;
+            if constexpr (STAGE_TAIL)
+                if (i == KVECS - 1 && idx >= NGRAN) continue;
             // row-major V, b128 store; column XOR by (row&8)<<1 keeps the
             // tr gather conflict-free under either half-wave pairing
             *reinterpret_cast<bf16x8*>(
@@ -453,12 +506,13 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
             // D=128: 64 scalar v_mul_f32; left to the compiler they become
             // 32 v_pk_mul_f32, slower beside the MFMAs there. D=64 measured
             // the other way round and keeps the packed form
-            // (scripts/attn_v6.hip, v3 against v2).
+            // (scripts/attn_v6.hip, v3 against v2). DH < D takes the scalar
+            // form in both classes (the same product bit for bit).
 #pragma unroll
             for (int n = 0; n < NV; ++n)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    if constexpr (D == 128)
+                    if constexpr (D == 128 || DH != D)
                         o_acc[n][r] = mul_f32_scalar(o_acc[n][r], alpha);
                     else
                         o_acc[n][r] *= alpha;
@@ -545,6 +599,18 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
             return 0ull;
         }
     };
+    // DH % 16 != 0: the last QK^T step reads K columns [DH, 16 * KK) of
+    // every row against zero Q, and 0 * garbage can be NaN: zero them once
+    // per buffer. Staging never writes them, and the first barrier of either
+    // loop below orders these stores ahead of the first read. V columns at
+    // or beyond DH are left as they are: a V column feeds its own output
+    // column only, and those are never stored.
+    if constexpr (KK * 16 > DH) {
+        static_assert(KK * 16 - DH == 8 && DBUF * KVBLK <= THREADS);
+        if (tid < DBUF * KVBLK)
+            *reinterpret_cast<bf16x8*>(&k_lds[tid * KPAD + DH]) =
+                bf16x8{0,0,0,0,0,0,0,0};
+    }
     // (the loads are written out at each site: wrapping tile_at + word_of +
     // issue_tile_loads in one more lambda reorders the unmasked code)
     if constexpr (DBUF == 2) {
@@ -638,12 +704,33 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
         for (int n = 0; n < NV; ++n) {
 #pragma unroll
             for (int r2 = 0; r2 < 4; ++r2) {
-                // dims n*32 + 8*r2 + 4*hi + (0..3) are consecutive
+                // dims n*32 + 8*r2 + 4*hi + (0..3) are consecutive; both
+                // halves of an 8-dim group lie below DH or neither does
+                // (DH % 8 == 0), so the last dim tile stores its groups
+                // below DH and nothing else (a quarter of it at DH = 40)
+                if (n * 32 + 8 * r2 >= DH) continue;
                 const int dim0 = n * 32 + 8 * r2 + 4 * hi;
                 unsigned short pack[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    pack[j] = EL::st(o_acc[n][r2 * 4 + j] * inv_l);
+                for (int j = 0; j < 4; ++j) {
+                    // DH < D: no packed f32, as above, and the roundings of
+                    // the class kernels, whose compiled epilogue rounds
+                    // values 1 and 2 of a group to fp32 ahead of the cast
+                    // (one v_pk_mul_f32) and casts the exact products 0 and
+                    // 3 (fp16: v_fma_mixlo_f16, one rounding; bf16 has no
+                    // such cast and rounds twice throughout). Both kinds
+                    // are pinned here by opaque instructions; what the
+                    // compiler makes of the class kernels is pinned by the
+                    // bit-equality test of the two routes.
+                    if (DH != D && (j == 1 || j == 2))
+                        pack[j] = EL::st(
+                            mul_f32_scalar(o_acc[n][r2 * 4 + j], inv_l));
+                    else if (DH != D)
+                        pack[j] = mul_cast_fused<E>(o_acc[n][r2 * 4 + j],
+                                                    inv_l);
+                    else
+                        pack[j] = EL::st(o_acc[n][r2 * 4 + j] * inv_l);
+                }
                 *reinterpret_cast<unsigned long long*>(
                     obase + orow * oss + dim0) =
                     *reinterpret_cast<unsigned long long*>(pack);
@@ -685,16 +772,57 @@ struct AttnArgs {
     long l_bs, l_hs, l_ss;
 };
 
-template <int D, bool MASKED, bool QLIST = false, bool LSE = false>
-static void launch_attn_v4(at::ScalarType st, dim3 grid, const AttnArgs& a) {
+// Head dims the attention kernels serve as they are, as X(head dim, tile
+// class): the one table behind the launch below, attn_head_dim_class and
+// attn_native_head_dims (which ops asks). A head dim below its class runs
+// the plain and key-masked kernels only; the block-list, log-sum-exp and
+// split flavours exist per class, and their callers zero-pad up to it.
+// One more head dim is one more line here.
+#define PA_ATTN_HEAD_DIMS(X) X(40, 64) X(64, 64) X(80, 128) X(128, 128)
+
+// Tile class of head dim D, 0 when the table has none.
+static int attn_head_dim_class(long D) {
+#define PA_X(DH_, CLS_) if (D == DH_) return CLS_;
+    PA_ATTN_HEAD_DIMS(PA_X)
+#undef PA_X
+    return 0;
+}
+
+std::vector<long> attn_native_head_dims() {
+    std::vector<long> dims;
+#define PA_X(DH_, CLS_) dims.push_back(DH_);
+    PA_ATTN_HEAD_DIMS(PA_X)
+#undef PA_X
+    return dims;
+}
+
+template <int D, bool MASKED, bool QLIST, bool LSE, int DH>
+static void launch_attn_v4_as(at::ScalarType st, dim3 grid,
+                              const AttnArgs& a) {
     PA_WITH_ELEM16(st, hipLaunchKernelGGL(
-        HIP_KERNEL_NAME(attn_fwd_v4_kernel<D, E, MASKED, QLIST, LSE>), grid,
-        dim3(512), 0,
+        HIP_KERNEL_NAME(attn_fwd_v4_kernel<D, E, MASKED, QLIST, LSE, DH>),
+        grid, dim3(512), 0,
         cur_stream(), (const E*)a.q, (const E*)a.k, (const E*)a.v, (E*)a.out,
         a.S, a.Sk, a.scale, a.H, a.q_bs, a.q_hs, a.q_ss, a.k_bs, a.k_hs,
         a.k_ss, a.v_bs, a.v_hs, a.v_ss, a.o_bs, a.o_hs, a.o_ss, a.xcd_grid,
         (E*)a.out2, a.s_split, a.o2_bs, a.o2_hs, a.o2_ss, a.mask_words,
         a.mask_live, a.mask_nlive, a.lse, a.l_bs, a.l_hs, a.l_ss));
+}
+
+// The table's instantiation for head dim D. The caller has checked that the
+// table holds D, and that a flavour beyond plain / key-masked comes with a
+// head dim that is its own class.
+template <bool MASKED, bool QLIST = false, bool LSE = false>
+static void launch_attn_v4(int D, at::ScalarType st, dim3 grid,
+                           const AttnArgs& a) {
+#define PA_X(DH_, CLS_)                                                     \
+    if constexpr (DH_ == CLS_ || (!QLIST && !LSE))                          \
+        if (D == DH_)                                                       \
+            return launch_attn_v4_as<CLS_, MASKED, QLIST, LSE, DH_>(st, grid, \
+                                                                    a);
+    PA_ATTN_HEAD_DIMS(PA_X)
+#undef PA_X
+    TORCH_CHECK(false, "attn_fwd: no kernel for head dim ", D);
 }
 
 // The one attention launcher. has_split (bshd only) writes rows >= split to
@@ -720,7 +848,9 @@ static std::vector<at::Tensor> attn_fwd_launch(
     const int b_ax = 0, s_ax = bshd ? 1 : 2, h_ax = bshd ? 2 : 1, d_ax = 3;
     const int B = (int)q.size(b_ax), S = (int)q.size(s_ax),
               H = (int)q.size(h_ax), D = (int)q.size(d_ax);
-    TORCH_CHECK(D == 64 || D == 128, "attn_fwd: D must be 64 or 128");
+    const int cls = attn_head_dim_class(D);
+    TORCH_CHECK(cls != 0, "attn_fwd: D must be 64 or 128, or one of the "
+                "native head dims below them (40, 80), got ", D);
     // The kernel indexes k and v with q's batch, head and dim counts: a k
     // or v with fewer of any is read past its end, never broadcast.
     TORCH_CHECK(k.size(b_ax) == B && v.size(b_ax) == B,
@@ -739,12 +869,31 @@ static std::vector<at::Tensor> attn_fwd_launch(
                               (km == nullptr || km->live.dim() != 3)),
                 "attn_fwd: the log-sum-exp output goes with neither a split "
                 "nor a block mask");
+    TORCH_CHECK(D == cls || (!has_split && !want_lse &&
+                             (km == nullptr || km->live.dim() != 3)),
+                "attn_fwd: head dim ", D, " runs the plain and key-masked "
+                "kernels only; zero-pad to ", cls, " for a split, the "
+                "log-sum-exp or a block mask");
     TORCH_CHECK(!has_split || (split > 0 && split < S),
                 "attn_fwd: split must lie inside (0, S = ", S, "), got ",
                 split);
     // The kernel's 16-byte vector loads need every stride a multiple of 8
     // elements and a 16-byte aligned base; anything else is copied once.
+    // A head dim below its class is refused instead: those calls exist to
+    // run on views without a copy, so a row start off 16 bytes is the
+    // caller's error there, reported before any launch.
     auto fix = [&](at::Tensor t) {
+        if (D != cls) {
+            TORCH_CHECK(
+                t.stride(d_ax) == 1 && (t.stride(s_ax) % 8) == 0 &&
+                    (t.stride(h_ax) % 8) == 0 && (t.stride(b_ax) % 8) == 0 &&
+                    (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0,
+                "attn_fwd: head dim ", D, " needs every row of q/k/v to "
+                "start on 16 bytes (base aligned, last dim contiguous, all "
+                "other strides multiples of 8 elements), got strides ",
+                t.strides());
+            return t;
+        }
         if (t.stride(d_ax) != 1 || (t.stride(s_ax) % 8) != 0 ||
             (t.stride(h_ax) % 8) != 0 || (t.stride(b_ax) % 8) != 0)
             t = t.contiguous();
@@ -838,25 +987,16 @@ static std::vector<at::Tensor> attn_fwd_launch(
         want_lse ? lse.stride(s_ax) : 0};
     const at::ScalarType st = qc.scalar_type();
     if (want_lse) {
-        if (km != nullptr) {
-            if (D == 128) launch_attn_v4<128, true, false, true>(st, grid, a);
-            else launch_attn_v4<64, true, false, true>(st, grid, a);
-        } else {
-            if (D == 128) launch_attn_v4<128, false, false, true>(st, grid, a);
-            else launch_attn_v4<64, false, false, true>(st, grid, a);
-        }
+        if (km != nullptr) launch_attn_v4<true, false, true>(D, st, grid, a);
+        else launch_attn_v4<false, false, true>(D, st, grid, a);
         return {out, lse};
     }
-    if (km != nullptr && km->live.dim() == 3) {
-        if (D == 128) launch_attn_v4<128, true, true>(st, grid, a);
-        else launch_attn_v4<64, true, true>(st, grid, a);
-    } else if (km != nullptr) {
-        if (D == 128) launch_attn_v4<128, true>(st, grid, a);
-        else launch_attn_v4<64, true>(st, grid, a);
-    } else {
-        if (D == 128) launch_attn_v4<128, false>(st, grid, a);
-        else launch_attn_v4<64, false>(st, grid, a);
-    }
+    if (km != nullptr && km->live.dim() == 3)
+        launch_attn_v4<true, true>(D, st, grid, a);
+    else if (km != nullptr)
+        launch_attn_v4<true>(D, st, grid, a);
+    else
+        launch_attn_v4<false>(D, st, grid, a);
     if (do_split) return {out, out2};
     return {out};
 }

@@ -59,6 +59,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "Fused flash attention fwd, bf16/fp16 MFMA (gfx950)");
     m.def("attn_fwd_bshd", &attn_fwd_bshd,
           "Fused flash attention fwd on [B,S,H,D] strided views (gfx950)");
+    m.def("attn_native_head_dims", &attn_native_head_dims,
+          "Head dims attn_fwd[_bshd][_masked] run without padding");
     m.def("attn_fwd_bshd_split", &attn_fwd_bshd_split,
           "Attention with per-stream split outputs [B,:split]/[B,split:]");
     m.def("pack_key_mask", &pack_key_mask,

@@ -23,6 +23,11 @@ kernel's overhead against --key-mask full), frame:W = the frame window of
 ops.frame_window_block_mask (needs --frames). The mask density — live
 256x64 blocks over all blocks — is printed beside each time.
 
+The sd15_* rows are SD1.5's head dims (8 heads over 320 / 640 channels, and
+the 77-token cross-attention). They run as the UNet calls them: ops.
+attention_bshd on [B, S, H, D] tensors, then .flatten(2). --only NAMES keeps
+the named rows of the table (comma-separated).
+
 --shape B,H,Sq,Sk,D runs that one shape instead of the table. --lse times
 ops.attention_lse (the LSE instantiations: one more store per row) in place
 of ops.attention; it takes no block mask.
@@ -103,6 +108,8 @@ def main():
                     help="run the WAN 720p shape with this many latent "
                          "frames (3600 tokens each) instead of the table")
     ap.add_argument("--shape", default="", metavar="B,H,Sq,Sk,D")
+    ap.add_argument("--only", default="", metavar="NAMES",
+                    help="comma-separated rows of the table to run")
     ap.add_argument("--lse", action="store_true",
                     help="time ops.attention_lse instead of ops.attention")
     ap.add_argument("--ring-chunks", type=int, default=0, metavar="N")
@@ -137,17 +144,32 @@ def main():
         args.frames * tokens_per_frame, 128)}
     if shape is not None:
         video = {"shape": shape}
-    for name, (B, H, S, Sk, D) in (video if args.frames > 0 or shape else {
+    table = video if args.frames > 0 or shape else {
         "flux_b8": (8, 24, 4608, 4608, 128),
         "flux_b1": (1, 24, 4608, 4608, 128),
         "sdxl_mid": (4, 20, 1024, 1024, 64),
         "square_2k": (16, 16, 2048, 2048, 128),
         "zimage_b21": (21, 28, 4352, 4352, 128),  # joint 256 txt + 4096 img
         "cross_512": (21, 28, 4096, 512, 128),    # padded text context
-    }).items():
+        "sd15_64": (8, 8, 4096, 4096, 40),        # 512 px, 64x64 latent
+        "sd15_32": (8, 8, 1024, 1024, 80),        # 32x32 level
+        "sd15_cross": (8, 8, 4096, 77, 40),       # CLIP context
+    }
+    if args.only:
+        names = args.only.split(",")
+        missing = [n for n in names if n not in table]
+        if missing:
+            ap.error(f"--only: no row named {missing}; rows: {list(table)}")
+        table = {n: table[n] for n in names}
+    for name, (B, H, S, Sk, D) in table.items():
+        bshd = name.startswith("sd15_")
+        if bshd and (args.lse or args.block_mask != "none"):
+            ap.error(f"{name} runs attention_bshd: no --lse, no block mask")
         q = torch.randn(B, H, S, D, device=dev, dtype=dtype)
         k = torch.randn(B, H, Sk, D, device=dev, dtype=dtype)
         v = torch.randn_like(k)
+        if bshd:
+            q, k, v = (t.view(B, -1, H, D) for t in (q, k, v))
         km = None
         if args.key_mask != "none":
             live = Sk if args.key_mask == "full" else min(args.live_keys, Sk)
@@ -162,7 +184,11 @@ def main():
                          args.frames, tokens_per_frame, window, device=dev))
             mk = {"block_mask": ops.pack_block_mask(block, B, S, Sk, km)}
             note = f"  density {block.float().mean().item():.4f}"
-        dt = timeit(lambda: attn(q, k, v, **mk), iters=10)
+        if bshd:
+            dt = timeit(lambda: ops.attention_bshd(q, k, v, **mk).flatten(2),
+                        iters=200, warmup=20)
+        else:
+            dt = timeit(lambda: attn(q, k, v, **mk), iters=10)
         tf = attn_flops(B, H, S, D, Sk) / dt / 1e12
         print(f"  {name:10s} B{B} H{H} S{S} Sk{Sk} D{D}: {dt*1e3:8.2f} ms  "
               f"{tf:7.1f} TF/s{note}")
