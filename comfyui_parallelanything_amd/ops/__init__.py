@@ -596,45 +596,101 @@ def _softmax_scale(q, scale: Optional[float]) -> float:
 _check_qkv = reference.check_qkv
 
 
-def _attn_native(q, k, v, scale: float, km, bshd: bool,
-                 split: Optional[int] = None):
-    """One attention call on the native kernels: (output, None), or
-    (None, why) when the call is not covered. ``why`` is None when there
-    is no extension to ask (PA_ALLOW_EAGER).
-
-    Picks ext.attn_fwd[_bshd][_split][_masked]; ``km`` is None, a KeyMask or
-    a BlockMask, whose 3-D ``live`` selects the block-list kernels inside
-    the masked entry points. Head dims 64/128 run as they are, and so do the
-    other head dims of the extension's table (40, 80) without a split or a
-    block mask; what is left of the 16-bit head dims under 128 is zero-padded
-    up, on the plain BSHD op only (see attention_bshd)."""
-    name = ("attn_fwd" + ("_bshd" if bshd else "")
+def _attn_op(bshd: bool, split=None, lse: bool = False) -> str:
+    """attn_fwd[_bshd][_split][_lse]: the op as _unsupported names it, and
+    the extension's binding up to its _masked suffix."""
+    return ("attn_fwd" + ("_bshd" if bshd else "")
             + ("_split" if split is not None else "")
-            + ("_masked" if km is not None else ""))
+            + ("_lse" if lse else ""))
+
+
+def _attn_head_dim(ext, q, km, bshd: bool, split=None, lse: bool = False):
+    """The head-dim rule: the head dim the kernels run this call at. That
+    is D itself for 64 and 128 (the two tile classes, in every flavour) and
+    for the other head dims of the extension's table (40, 80) on plain and
+    key-masked calls; 64 or 128, to zero-pad to, for what is left of the
+    16-bit head dims under 128 on the un-split BSHD ops (see attention_bshd);
+    None when the call is not covered."""
+    D = q.shape[-1]
+    if q.dtype not in _NATIVE16:
+        return None
+    plain = split is None and not lse and not isinstance(km, BlockMask)
+    if D in (64, 128) or (plain and D in ext.attn_native_head_dims()):
+        return D
+    if D < 128 and bshd and split is None:
+        return 64 if D <= 64 else 128
+    return None
+
+
+def _attn_native(q, k, v, scale: float, km, bshd: bool,
+                 split: Optional[int] = None, lse: bool = False):
+    """One attention call on the native kernels: (result, None), or
+    (None, why) when the call is not covered. ``why`` is None when there
+    is no extension to ask (PA_ALLOW_EAGER). ``result`` is the output, the
+    two outputs with ``split``, (out, lse) with ``lse``.
+
+    Picks ext.attn_fwd[_bshd][_split][_lse][_masked]; ``km`` is None, a
+    KeyMask or a BlockMask, whose 3-D ``live`` selects the block-list
+    kernels inside the masked entry points."""
+    name = _attn_op(bshd, split, lse) + ("_masked" if km is not None else "")
     ext = _require_ext(name)
     if ext is None:
         return None, None
-    fn = getattr(ext, name)
+    D = q.shape[-1]
+    width = _attn_head_dim(ext, q, km, bshd, split, lse)
+    if width is None:
+        return None, f"dtype={q.dtype}, D={D}"
     args = (float(scale),)
     if split is not None:
         args += (int(split),)
     if km is not None:
         args += (km.words, km.live, km.nlive)
-    D = q.shape[-1]
-    native = D in (64, 128) or (
-        split is None and (km is None or isinstance(km, KeyMask))
-        and D in ext.attn_native_head_dims())
-    if q.dtype in _NATIVE16 and native:
-        if not bshd:
-            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        return fn(q, k, v, *args), None
-    if q.dtype in _NATIVE16 and D < 128 and bshd and split is None:
-        pad = (0, (64 if D <= 64 else 128) - D)
-        out = fn(torch.nn.functional.pad(q, pad),
-                 torch.nn.functional.pad(k, pad),
-                 torch.nn.functional.pad(v, pad), *args)
-        return out[..., :D], None
-    return None, f"dtype={q.dtype}, D={D}"
+    if width != D:
+        q, k, v = (torch.nn.functional.pad(t, (0, width - D))
+                   for t in (q, k, v))
+    elif not bshd:
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    res = getattr(ext, name)(q, k, v, *args)
+    if width == D:
+        return (tuple(res) if lse or split is not None else res), None
+    # padding q and k leaves every score, so the lse, unchanged; the padded
+    # v columns come off the output
+    return ((res[0][..., :D], res[1]) if lse else res[..., :D]), None
+
+
+def _attention(q, k, v, scale, key_mask, block_mask, *, bshd: bool,
+               split: Optional[int] = None, lse: bool = False):
+    """The body of the five public ops: check, pack the mask, run the native
+    kernels, else note the gap and take the reference path."""
+    Sq, Sk = _check_qkv(q, k, v, bshd=bshd, split=split)
+    scale = _softmax_scale(q, scale)
+    km = _mask_for(key_mask, block_mask, q, Sq, Sk)
+    why = None
+    if q.is_cuda:
+        res, why = _attn_native(q, k, v, scale, km, bshd, split, lse)
+        if res is not None:
+            return res
+    if split is not None:
+        # Composed from the un-split op, which is also how a split call
+        # reaches the native head dims and the zero-pad route: that is no
+        # reference-path fallback. One that is, is noted here (unmasked
+        # calls only) and by the un-split op.
+        if (why is not None and km is None
+                and _attn_head_dim(hip_ext(), q, km, bshd) is None):
+            _unsupported(_attn_op(bshd, split), why)
+        packed = (None, km) if isinstance(km, BlockMask) else (km, None)
+        out = _attention(q, k, v, scale, *packed, bshd=bshd)
+        return out[:, :split].contiguous(), out[:, split:].contiguous()
+    if why is not None:
+        _unsupported(_attn_op(bshd, lse=lse), why)
+    if bshd:
+        q, k, v = (t.permute(0, 2, 1, 3) for t in (q, k, v))
+    res = reference.attention(q, k, v, scale, return_lse=lse, **_mask_kw(km))
+    if not bshd:
+        return res
+    if not lse:
+        return res.permute(0, 2, 1, 3)
+    return res[0].permute(0, 2, 1, 3), res[1].permute(0, 2, 1).contiguous()
 
 
 def attention(q, k, v, scale: Optional[float] = None,
@@ -651,16 +707,7 @@ def attention(q, k, v, scale: Optional[float] = None,
     k and v have q's batch, head count and head dim and one length Sk;
     anything else raises ValueError (nothing is broadcast). B, H or Sq of
     zero returns the empty result, Sk = 0 zeros: no row sees a key."""
-    Sq, Sk = _check_qkv(q, k, v, bshd=False)
-    scale = _softmax_scale(q, scale)
-    km = _mask_for(key_mask, block_mask, q, Sq, Sk)
-    if q.is_cuda:
-        out, why = _attn_native(q, k, v, scale, km, bshd=False)
-        if out is not None:
-            return out
-        if why is not None:
-            _unsupported("attn_fwd", why)
-    return reference.attention(q, k, v, scale, **_mask_kw(km))
+    return _attention(q, k, v, scale, key_mask, block_mask, bshd=False)
 
 
 def attention_bshd(q, k, v, scale: Optional[float] = None,
@@ -691,20 +738,7 @@ def attention_bshd(q, k, v, scale: Optional[float] = None,
     need a 256-class tile that does not exist: they take the reference path
     with a warning.
     """
-    Sq, Sk = _check_qkv(q, k, v, bshd=True)
-    scale = _softmax_scale(q, scale)
-    km = _mask_for(key_mask, block_mask, q, Sq, Sk)
-    if q.is_cuda:
-        out, why = _attn_native(q, k, v, scale, km, bshd=True)
-        if out is not None:
-            return out
-        if why is not None:
-            _unsupported("attn_fwd_bshd", why)
-    out = reference.attention(
-        q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3),
-        scale, **_mask_kw(km),
-    )
-    return out.permute(0, 2, 1, 3)
+    return _attention(q, k, v, scale, key_mask, block_mask, bshd=True)
 
 
 def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None,
@@ -712,60 +746,13 @@ def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None,
     """attention_bshd with per-stream outputs: rows [:split] and [split:]
     land in two contiguous tensors (feeds dual-stream projections with no
     reshape copies). key_mask and block_mask as in attention_bshd."""
-    Sq, Sk = _check_qkv(q, k, v, bshd=True, split=split)
-    scale = _softmax_scale(q, scale)
-    km = _mask_for(key_mask, block_mask, q, Sq, Sk)
-    if q.is_cuda:
-        out, why = _attn_native(q, k, v, scale, km, bshd=True, split=split)
-        if out is not None:
-            a, b = out
-            return a, b
-        # 16-bit head dims below 128 still run the native kernel through
-        # attention_bshd's zero-pad route (only the split epilogue is
-        # composed from slices) — that is no reference-path fallback.
-        # Anything else is reported here (unmasked) and by attention_bshd.
-        padded = (why is not None and q.dtype in _NATIVE16
-                  and q.shape[-1] < 128)
-        if km is None and not padded:
-            _unsupported("attn_fwd_bshd_split",
-                         f"dtype={q.dtype}, D={q.shape[-1]}")
-    if isinstance(km, BlockMask):
-        out = attention_bshd(q, k, v, scale, block_mask=km)
-    else:
-        out = attention_bshd(q, k, v, scale, km)
-    return out[:, :split].contiguous(), out[:, split:].contiguous()
+    return _attention(q, k, v, scale, key_mask, block_mask, bshd=True,
+                      split=split)
 
 
 _NO_BLOCK_LSE = ("block masks are not supported together with the "
                  "log-sum-exp output (attention_lse / attention_bshd_lse take "
                  "key_mask= only)")
-
-
-def _attn_lse_native(q, k, v, scale: float, km, bshd: bool):
-    """_attn_native for the LSE entry points ext.attn_fwd[_bshd]_lse[_masked]:
-    ((out, lse), None) or (None, why). The D < 128 zero-pad route is the
-    plain BSHD op's: padding q and k leaves every score, so the lse,
-    unchanged."""
-    name = ("attn_fwd" + ("_bshd" if bshd else "") + "_lse"
-            + ("_masked" if km is not None else ""))
-    ext = _require_ext(name)
-    if ext is None:
-        return None, None
-    fn = getattr(ext, name)
-    args = (float(scale),)
-    if km is not None:
-        args += (km.words, km.live, km.nlive)
-    D = q.shape[-1]
-    if q.dtype in _NATIVE16 and D in (64, 128):
-        if not bshd:
-            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        return tuple(fn(q, k, v, *args)), None
-    if q.dtype in _NATIVE16 and D < 128 and bshd:
-        pad = (0, (64 if D <= 64 else 128) - D)
-        out, lse = fn(*(torch.nn.functional.pad(t, pad) for t in (q, k, v)),
-                      *args)
-        return (out[..., :D], lse), None
-    return None, f"dtype={q.dtype}, D={D}"
 
 
 def attention_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
@@ -781,17 +768,7 @@ def attention_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
     supported."""
     if block_mask is not None:
         raise ValueError(f"attention_lse: {_NO_BLOCK_LSE}")
-    Sq, Sk = _check_qkv(q, k, v, bshd=False)
-    scale = _softmax_scale(q, scale)
-    km = _mask_for(key_mask, None, q, Sq, Sk)
-    if q.is_cuda:
-        res, why = _attn_lse_native(q, k, v, scale, km, bshd=False)
-        if res is not None:
-            return res
-        if why is not None:
-            _unsupported("attn_fwd_lse", why)
-    return reference.attention(q, k, v, scale, return_lse=True,
-                               **_mask_kw(km))
+    return _attention(q, k, v, scale, key_mask, None, bshd=False, lse=True)
 
 
 def attention_bshd_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
@@ -801,19 +778,7 @@ def attention_bshd_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
     under 128 work as in attention_bshd."""
     if block_mask is not None:
         raise ValueError(f"attention_bshd_lse: {_NO_BLOCK_LSE}")
-    Sq, Sk = _check_qkv(q, k, v, bshd=True)
-    scale = _softmax_scale(q, scale)
-    km = _mask_for(key_mask, None, q, Sq, Sk)
-    if q.is_cuda:
-        res, why = _attn_lse_native(q, k, v, scale, km, bshd=True)
-        if res is not None:
-            return res
-        if why is not None:
-            _unsupported("attn_fwd_bshd_lse", why)
-    out, lse = reference.attention(
-        q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3),
-        scale, return_lse=True, **_mask_kw(km))
-    return out.permute(0, 2, 1, 3), lse.permute(0, 2, 1).contiguous()
+    return _attention(q, k, v, scale, key_mask, None, bshd=True, lse=True)
 
 
 ATTN_MERGE_MAX = reference.MERGE_MAX    # partials per merge: a node's GPUs

@@ -314,46 +314,36 @@ def attention(
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     dtype = q.dtype
+    B, Sq, Sk = q.shape[0], q.shape[2], k.shape[2]
+    # vis: which keys each query row sees, broadcast over [B, H, Sq, Sk];
+    # None = all of them
+    vis = None
     if block_mask is not None:
-        Sq, Sk = q.shape[2], k.shape[2]
         bm = as_bool_block_mask(block_mask, Sq, Sk).to(q.device)
         vis = bm.repeat_interleave(Q_BLOCK, dim=0).repeat_interleave(
             KV_TILE, dim=1)[None, None, :Sq, :Sk]       # [1, 1, Sq, Sk]
-        if key_mask is not None:
-            m = as_bool_key_mask(key_mask).to(q.device)
-            if m.shape != (q.shape[0], Sk):
-                raise ValueError(f"key mask {tuple(m.shape)} does not match "
-                                 f"[B={q.shape[0]}, Sk={Sk}]")
-            vis = vis & m[:, None, None, :]             # [B, 1, Sq, Sk]
+    if key_mask is not None:
+        m = as_bool_key_mask(key_mask).to(q.device)
+        if m.shape != (B, Sk):
+            raise ValueError(f"key mask {tuple(m.shape)} does not match "
+                             f"[B={B}, Sk={Sk}]")
+        m = m[:, None, None, :]                         # [B, 1, 1, Sk]
+        vis = m if vis is None else vis & m
+    qf, kf, vf = _wide(q), _wide(k), _wide(v)
+    if vis is not None:
+        # Unmasked calls skip this: a copy of k or v can take matmul down
+        # another path and change bits.
         seen = vis.any(dim=2)[..., None]                # [B|1, 1, Sk, 1]
-        kf = torch.where(seen, _wide(k), torch.zeros((), device=k.device))
-        vf = torch.where(seen, _wide(v), torch.zeros((), device=v.device))
-        s = torch.matmul(_wide(q), kf.transpose(-1, -2)) * scale
+        kf = torch.where(seen, kf, torch.zeros((), device=k.device))
+        vf = torch.where(seen, vf, torch.zeros((), device=v.device))
+    s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
+    if vis is not None:
         s = s.masked_fill(~vis, float("-inf"))
-        p = torch.softmax(s, dim=-1)
+    p = torch.softmax(s, dim=-1)
+    if vis is not None:
         # a row with no visible key: softmax over all -inf is NaN -> zeros
         p = torch.where(vis.any(dim=3, keepdim=True), p,
                         torch.zeros((), device=p.device))
-        out = torch.matmul(p, vf).to(dtype)
-        return (out, torch.logsumexp(s, dim=-1)) if return_lse else out
-    if key_mask is None:
-        s = torch.matmul(_wide(q), _wide(k).transpose(-1, -2)) * scale
-        p = torch.softmax(s, dim=-1)
-        out = torch.matmul(p, _wide(v)).to(dtype)
-        return (out, torch.logsumexp(s, dim=-1)) if return_lse else out
-    m = as_bool_key_mask(key_mask).to(q.device)
-    if m.shape != (q.shape[0], k.shape[2]):
-        raise ValueError(f"key mask {tuple(m.shape)} does not match "
-                         f"[B={q.shape[0]}, Sk={k.shape[2]}]")
-    rows = m[:, None, :, None]                      # [B, 1, Sk, 1]
-    kf = torch.where(rows, _wide(k), torch.zeros((), device=k.device))
-    vf = torch.where(rows, _wide(v), torch.zeros((), device=v.device))
-    s = torch.matmul(_wide(q), kf.transpose(-1, -2)) * scale
-    s = s.masked_fill(~m[:, None, None, :], float("-inf"))
-    p = torch.softmax(s, dim=-1)
-    # all keys masked: softmax over all -inf is NaN; the contract is zeros
-    p = torch.where(m.any(dim=1)[:, None, None, None], p,
-                    torch.zeros((), device=p.device))
     out = torch.matmul(p, vf).to(dtype)
     # logsumexp of a row of -inf is -inf (of an empty row too)
     return (out, torch.logsumexp(s, dim=-1)) if return_lse else out
