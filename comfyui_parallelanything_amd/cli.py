@@ -55,6 +55,10 @@ def main(argv=None):
     ap.add_argument("--frame-window", type=int, default=None, metavar="N",
                     help="wan models: block-sparse self-attention over "
                          "frames within N of the query's (default: dense)")
+    ap.add_argument("--frame-span", default=None, metavar="BACK,AHEAD",
+                    help="wan models: every token attends exactly the "
+                         "frames BACK before to AHEAD after its own; BACK "
+                         "may be 'all' (all,0 = frame-causal)")
     ap.add_argument("--channels-last", action="store_true",
                     help="sd15 / sdxl: keep activations and conv weights "
                          "channels-last (NHWC GroupNorm kernels, token "
@@ -72,6 +76,20 @@ def main(argv=None):
             ap.error("--frame-window applies to wan models only")
         if args.frame_window < 0:
             ap.error("--frame-window must be >= 0")
+    frame_span = None
+    if args.frame_span is not None:
+        if not args.model.startswith("wan"):
+            ap.error("--frame-span applies to wan models only")
+        if args.frame_window is not None:
+            ap.error("--frame-span and --frame-window exclude each other")
+        try:
+            back, ahead = args.frame_span.split(",")
+            frame_span = (None if back == "all" else int(back), int(ahead))
+        except ValueError:
+            ap.error("--frame-span takes BACK,AHEAD (BACK an integer or "
+                     "'all')")
+        if frame_span[1] < 0 or (frame_span[0] or 0) < 0:
+            ap.error("--frame-span values must be >= 0")
     if args.channels_last and args.model not in ("sd15", "sdxl"):
         ap.error("--channels-last applies to sd15 and sdxl only")
     if args.token_ops and args.model not in ("sd15", "sdxl"):
@@ -104,6 +122,8 @@ def main(argv=None):
     model = make(dev=chain.lead, dtype=dtype, tiny=tiny, **layout)
     if args.frame_window is not None:
         model.cfg.self_attn_frame_window = args.frame_window
+    if frame_span is not None:
+        model.cfg.self_attn_frame_span = frame_span
 
     if args.lora:
         from .models.lora import merge_lora_file
@@ -155,6 +175,7 @@ def main(argv=None):
         "dtype": str(dtype).replace("torch.", ""), "tiny": tiny,
         "engine": "in-process", "text_len": text_len,
         "frame_window": args.frame_window,
+        "frame_span": frame_span,
     }
     print(json.dumps(summary, indent=2))
     if args.json_out:

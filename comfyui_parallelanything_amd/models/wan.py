@@ -56,12 +56,14 @@ class WanBlock(nn.Module):
         self.ffn = FusedMLP(dim, ffn_dim, dim)
 
     def forward(self, x, e, context, pe, key_mask=None, block_mask=None,
-                self_attn=None):
+                self_attn=None, row_bounds=None):
         # e: [B, 6, dim] time-modulation; learned bias added per block
         # key_mask: optional ops.KeyMask over the context tokens — masks the
         # cross-attention only
         # block_mask: optional ops.BlockMask over the space-time tokens —
         # sparsifies the self-attention only (WanConfig.self_attn_frame_window)
+        # row_bounds: optional ops.RowBounds over the space-time tokens — the
+        # self-attention's exact frame span (WanConfig.self_attn_frame_span)
         # self_attn: optional (q, k, v, scale) -> [B,S,H,D] in place of the
         # local self-attention: x is a token shard and the keys live on other
         # ranks (parallel.sequence)
@@ -78,7 +80,8 @@ class WanBlock(nn.Module):
         )
         if self_attn is None:
             attn = ops.attention_bshd(q, k, v, self.scale,
-                                      block_mask=block_mask)
+                                      block_mask=block_mask,
+                                      row_bounds=row_bounds)
         else:
             attn = self_attn(q, k, v, self.scale)
         attn = attn.flatten(2)
@@ -121,6 +124,13 @@ class WanConfig:
     # of its own (ops.frame_window_block_mask). None, or a window that
     # reaches every frame (>= frames - 1), is dense attention.
     self_attn_frame_window: Optional[int] = None
+    # Exact frame span (back, ahead): a token of frame f attends the frames
+    # f - back .. f + ahead and nothing else (ops.frame_span_row_bounds),
+    # whatever the kernel's geometry. back = None reaches every earlier
+    # frame: (None, 0) is frame-causal attention, (W, W) the exact +-W
+    # window. None, or a span that reaches every frame, is dense attention.
+    # Not together with self_attn_frame_window.
+    self_attn_frame_span: Optional[Tuple[Optional[int], int]] = None
 
     @classmethod
     def wan22_a14b(cls) -> "WanConfig":
@@ -170,7 +180,7 @@ class WanDiT(nn.Module):
         self.head_mod = nn.Linear(cfg.dim, cfg.dim * 2)
         self.head = nn.Linear(cfg.dim, self.patch_dim)
         self._pe_cache: dict = {}
-        self._mask_cache: dict = {}  # packed frame-window BlockMasks
+        self._mask_cache: dict = {}  # packed BlockMasks and RowBounds
         # set by parallel.sequence.install_sequence_parallel; None = every
         # token on this device
         self._seq_parallel = None
@@ -197,6 +207,31 @@ class WanDiT(nn.Module):
             self._mask_cache[key] = bm
         return bm
 
+    def _frame_span_bounds(self, f, tokens_per_frame, device):
+        """The packed self-attention RowBounds, or None for dense attention.
+        Packed once per (grid, span, device)."""
+        span = self.cfg.self_attn_frame_span
+        if span is None:
+            return None
+        if self.cfg.self_attn_frame_window is not None:
+            raise ValueError("self_attn_frame_span and self_attn_frame_window "
+                             "are two definitions of one mask: set one")
+        back, ahead = span
+        if ahead < 0 or (back is not None and back < 0):
+            raise ValueError(f"self_attn_frame_span must be (back >= 0 or "
+                             f"None, ahead >= 0), got {span}")
+        if (back is None or back >= f - 1) and ahead >= f - 1:
+            return None
+        key = ("span", f, tokens_per_frame, back, ahead, str(device))
+        rb = self._mask_cache.get(key)
+        if rb is None:
+            S = f * tokens_per_frame
+            rb = ops.pack_row_bounds(
+                *ops.frame_span_row_bounds(f, tokens_per_frame, back, ahead,
+                                           device=device), S, S)
+            self._mask_cache[key] = rb
+        return rb
+
     def _pe(self, f, h, w, device):
         key = (f, h, w, str(device))
         pe = self._pe_cache.get(key)
@@ -215,6 +250,10 @@ class WanDiT(nn.Module):
                 raise ValueError(
                     "self_attn_frame_window with sequence parallelism is "
                     "not supported: the ring has no block masks")
+            if cfg.self_attn_frame_span is not None:
+                raise ValueError(
+                    "self_attn_frame_span with sequence parallelism is not "
+                    "supported: the ring has no row bounds")
             x, timesteps, context, image_cond, attention_mask = sp.broadcast(
                 x, timesteps, context, image_cond, attention_mask)
         B, C, F, H, W = x.shape
@@ -260,6 +299,9 @@ class WanDiT(nn.Module):
         bm = self._frame_window_mask(B, f, h * w, x.device)
         if bm is not None:
             mk["block_mask"] = bm
+        rb = self._frame_span_bounds(f, h * w, x.device)
+        if rb is not None:
+            mk["row_bounds"] = rb
         if sp is not None:
             mk["self_attn"] = sp.attention
         for block in self.transformer_blocks:

@@ -561,9 +561,112 @@ def _block_mask_for(block_mask, key_mask, q, Sq: int, Sk: int) -> BlockMask:
     return bm
 
 
-def _mask_for(key_mask, block_mask, q, Sq: int, Sk: int):
-    """The call's packed mask: None, a KeyMask or a BlockMask (which holds
-    the key mask too)."""
+@dataclass
+class RowBounds:
+    """Per-row key ranges packed for the row-bounds attention kernels: query
+    row i sees the keys lo[i] <= j < hi[i], for all batch elements and heads.
+
+    Tensors, plus the two lengths the pack was made for (checked before
+    every launch; parallel.pipeline's recursive move carries the tensors
+    across devices and leaves the integers as they are):
+      lo, hi      the [Sq] integer bounds as given
+      lo_c, hi_c  [Sq] int32, clamped to [0, Sk]
+      range       [ceil(Sq/256), 4] int32 per query block, in 64-key tiles:
+                  t0, t1 the tiles it walks, f0, f1 those every row of it
+                  sees whole (ops/hip/attention.h, pack_row_bounds_kernel)
+    On CPU only ``lo`` and ``hi`` are set. ``range`` drives the kernel's
+    K/V loads, so the pack kernel is its only producer: build one with
+    pack_row_bounds, never by hand.
+    """
+    lo: torch.Tensor
+    hi: torch.Tensor
+    lo_c: Optional[torch.Tensor] = None
+    hi_c: Optional[torch.Tensor] = None
+    range: Optional[torch.Tensor] = None
+    Sq: int = 0
+    Sk: int = 0
+
+
+def pack_row_bounds(lo, hi, Sq: int, Sk: int) -> RowBounds:
+    """Pack per-row key ranges once, for any number of attention calls of
+    those lengths: lo and hi are [Sq] integer tensors on q's device, shared
+    by all batch elements and heads.
+
+    Contract of every ``row_bounds=`` argument below: key j is visible to
+    query row i iff lo[i] <= j < hi[i] and j < Sk. The bounds are clamped to
+    [0, Sk] on the device (nothing is read on the host, so pack + attention
+    capture into one graph); a row with lo >= hi after clamping sees no key
+    and returns zeros. Floating or bool tensors raise, as in pack_key_mask;
+    another rank or length raises ValueError. K/V rows at or beyond Sk are
+    don't-care, and K/V rows in 64-key tiles that no row of a 256-row query
+    block reaches are never loaded for that block; K/V inside [0, Sk) must
+    otherwise be finite, because a key one row does not see is still
+    multiplied, by p = 0, where another row of its block sees that tile.
+    Not supported: together with key_mask= or block_mask=, in
+    attention_bshd_split, in the _lse ops (ValueError each), per-head or
+    per-batch bounds.
+    """
+    Sq, Sk = int(Sq), int(Sk)
+    reference.check_row_bounds(lo, hi, Sq)
+    if lo.is_cuda:
+        ext = _require_ext("pack_row_bounds")
+        if ext is not None:
+            lo_c, hi_c, rng = ext.pack_row_bounds(lo, hi, Sk)
+            return RowBounds(lo, hi, lo_c, hi_c, rng, Sq, Sk)
+    return RowBounds(lo, hi, Sq=Sq, Sk=Sk)
+
+
+def causal_row_bounds(Sq: int, Sk: int, device=None):
+    """(lo, hi) of causal attention, bottom-right aligned: lo = 0, hi[i] =
+    i + 1 + Sk - Sq (the last query row sees every key)."""
+    i = torch.arange(int(Sq), device=device, dtype=torch.int64)
+    return torch.zeros_like(i), i + (1 + int(Sk) - int(Sq))
+
+
+def frame_span_row_bounds(frames: int, tokens_per_frame: int, back, ahead: int,
+                          device=None):
+    """(lo, hi) for video tokens in (frame, row, col) order, S = frames *
+    tokens_per_frame: the token of frame f sees exactly the frames f - back
+    .. f + ahead, lo[i] = max(0, f - back) * T and hi[i] = min(frames, f +
+    ahead + 1) * T with f = i // T. back=None reaches every earlier frame
+    (lo = 0): (None, 0) is frame-causal attention, (W, W) the +-W window."""
+    frames, T, ahead = int(frames), int(tokens_per_frame), int(ahead)
+    if frames < 1 or T < 1 or ahead < 0 or (back is not None and back < 0):
+        raise ValueError(f"frame_span_row_bounds: frames={frames}, "
+                         f"tokens_per_frame={T}, back={back}, ahead={ahead}")
+    f = torch.arange(frames * T, device=device, dtype=torch.int64) // T
+    lo = (torch.zeros_like(f) if back is None
+          else torch.clamp(f - int(back), min=0) * T)
+    return lo, torch.clamp(f + ahead + 1, max=frames) * T
+
+
+def _row_bounds_for(row_bounds, q, Sq: int, Sk: int) -> RowBounds:
+    rb = row_bounds
+    if not isinstance(rb, RowBounds):
+        rb = pack_row_bounds(*rb, Sq, Sk)
+    elif (rb.Sq, rb.Sk) != (Sq, Sk):
+        raise ValueError(f"RowBounds was packed for (Sq, Sk) = "
+                         f"{(rb.Sq, rb.Sk)}, this call has {(Sq, Sk)}")
+    if rb.lo.device != q.device or rb.hi.device != q.device:
+        raise ValueError(f"row bounds on {rb.lo.device}, q on {q.device}")
+    if q.is_cuda and rb.range is None:
+        # packed on CPU (or under PA_ALLOW_EAGER) and moved: pack here
+        rb = pack_row_bounds(rb.lo, rb.hi, Sq, Sk)
+    return rb
+
+
+_NO_ROW_BOUNDS = ("row_bounds= is not supported in {} (attention and "
+                  "attention_bshd take it)")
+
+
+def _mask_for(key_mask, block_mask, q, Sq: int, Sk: int, row_bounds=None):
+    """The call's packed mask: None, a KeyMask, a BlockMask (which holds
+    the key mask too) or a RowBounds."""
+    if row_bounds is not None:
+        if key_mask is not None or block_mask is not None:
+            raise ValueError(
+                f"attention: {reference.NO_ROW_BOUNDS_WITH_MASK}")
+        return _row_bounds_for(row_bounds, q, Sq, Sk)
     if block_mask is not None:
         return _block_mask_for(block_mask, key_mask, q, Sq, Sk)
     return None if key_mask is None else _key_mask_for(key_mask, q)
@@ -573,6 +676,8 @@ def _mask_kw(km) -> dict:
     """``km`` as keyword arguments of reference.attention / ops.attention*."""
     if isinstance(km, BlockMask):
         return {"key_mask": km.keys, "block_mask": km.block}
+    if isinstance(km, RowBounds):
+        return {"row_bounds": (km.lo, km.hi)}
     return {"key_mask": None if km is None else km.mask}
 
 
@@ -598,7 +703,7 @@ _check_qkv = reference.check_qkv
 
 def _attn_op(bshd: bool, split=None, lse: bool = False) -> str:
     """attn_fwd[_bshd][_split][_lse]: the op as _unsupported names it, and
-    the extension's binding up to its _masked suffix."""
+    the extension's binding up to its _masked / _band suffix."""
     return ("attn_fwd" + ("_bshd" if bshd else "")
             + ("_split" if split is not None else "")
             + ("_lse" if lse else ""))
@@ -610,11 +715,13 @@ def _attn_head_dim(ext, q, km, bshd: bool, split=None, lse: bool = False):
     for the other head dims of the extension's table (40, 80) on plain and
     key-masked calls; 64 or 128, to zero-pad to, for what is left of the
     16-bit head dims under 128 on the un-split BSHD ops (see attention_bshd);
-    None when the call is not covered."""
+    None when the call is not covered. Row bounds follow the block masks'
+    rule: 40 and 80 are padded."""
     D = q.shape[-1]
     if q.dtype not in _NATIVE16:
         return None
-    plain = split is None and not lse and not isinstance(km, BlockMask)
+    plain = (split is None and not lse
+             and not isinstance(km, (BlockMask, RowBounds)))
     if D in (64, 128) or (plain and D in ext.attn_native_head_dims()):
         return D
     if D < 128 and bshd and split is None:
@@ -630,9 +737,12 @@ def _attn_native(q, k, v, scale: float, km, bshd: bool,
     two outputs with ``split``, (out, lse) with ``lse``.
 
     Picks ext.attn_fwd[_bshd][_split][_lse][_masked]; ``km`` is None, a
-    KeyMask or a BlockMask, whose 3-D ``live`` selects the block-list
-    kernels inside the masked entry points."""
-    name = _attn_op(bshd, split, lse) + ("_masked" if km is not None else "")
+    KeyMask, a BlockMask, whose 3-D ``live`` selects the block-list
+    kernels inside the masked entry points, or a RowBounds, which has the
+    _band entry points."""
+    band = isinstance(km, RowBounds)
+    name = _attn_op(bshd, split, lse) + (
+        "_band" if band else "_masked" if km is not None else "")
     ext = _require_ext(name)
     if ext is None:
         return None, None
@@ -643,7 +753,9 @@ def _attn_native(q, k, v, scale: float, km, bshd: bool,
     args = (float(scale),)
     if split is not None:
         args += (int(split),)
-    if km is not None:
+    if band:
+        args += (km.lo_c, km.hi_c, km.range)
+    elif km is not None:
         args += (km.words, km.live, km.nlive)
     if width != D:
         q, k, v = (torch.nn.functional.pad(t, (0, width - D))
@@ -659,12 +771,13 @@ def _attn_native(q, k, v, scale: float, km, bshd: bool,
 
 
 def _attention(q, k, v, scale, key_mask, block_mask, *, bshd: bool,
-               split: Optional[int] = None, lse: bool = False):
+               split: Optional[int] = None, lse: bool = False,
+               row_bounds=None):
     """The body of the five public ops: check, pack the mask, run the native
     kernels, else note the gap and take the reference path."""
     Sq, Sk = _check_qkv(q, k, v, bshd=bshd, split=split)
     scale = _softmax_scale(q, scale)
-    km = _mask_for(key_mask, block_mask, q, Sq, Sk)
+    km = _mask_for(key_mask, block_mask, q, Sq, Sk, row_bounds)
     why = None
     if q.is_cuda:
         res, why = _attn_native(q, k, v, scale, km, bshd, split, lse)
@@ -694,7 +807,7 @@ def _attention(q, k, v, scale, key_mask, block_mask, *, bshd: bool,
 
 
 def attention(q, k, v, scale: Optional[float] = None,
-              key_mask=None, block_mask=None) -> torch.Tensor:
+              key_mask=None, block_mask=None, row_bounds=None) -> torch.Tensor:
     """Flash-style fused attention, layout [B, H, S, D].
 
     key_mask: optional KeyMask or raw [B, Sk] bool/integer mask (see
@@ -703,21 +816,29 @@ def attention(q, k, v, scale: Optional[float] = None,
     bool/integer mask (see pack_block_mask for the contract). A raw one is
     packed per call, together with key_mask; a packed one already holds its
     key mask, and passing key_mask= beside it raises.
+    row_bounds: optional RowBounds or raw (lo, hi) pair of [Sq] integer
+    tensors, query row i seeing the keys lo[i] <= j < hi[i] (see
+    pack_row_bounds for the contract; causal_row_bounds and
+    frame_span_row_bounds build the usual ones). A raw pair is packed per
+    call. Together with key_mask= or block_mask= it raises ValueError.
 
     k and v have q's batch, head count and head dim and one length Sk;
     anything else raises ValueError (nothing is broadcast). B, H or Sq of
     zero returns the empty result, Sk = 0 zeros: no row sees a key."""
-    return _attention(q, k, v, scale, key_mask, block_mask, bshd=False)
+    return _attention(q, k, v, scale, key_mask, block_mask, bshd=False,
+                      row_bounds=row_bounds)
 
 
 def attention_bshd(q, k, v, scale: Optional[float] = None,
-                   key_mask=None, block_mask=None) -> torch.Tensor:
+                   key_mask=None, block_mask=None,
+                   row_bounds=None) -> torch.Tensor:
     """Fused attention on [B, S, H, D] (strided views allowed — e.g. slices
     of a fused qkv projection; no transpose/contiguous copies on GPU).
 
     key_mask: optional KeyMask or raw [B, Sk] bool/integer mask (see
     pack_key_mask for the contract). block_mask: optional BlockMask or raw
-    [ceil(Sq/256), ceil(Sk/64)] mask, as in attention.
+    [ceil(Sq/256), ceil(Sk/64)] mask, row_bounds: optional RowBounds or raw
+    (lo, hi) pair, both as in attention.
 
     Head dims. 64 and 128 are the kernel's two tile classes. SD1.5's 40 and
     80 have kernels of their own inside those classes (docs/KERNELS.md,
@@ -727,7 +848,7 @@ def attention_bshd(q, k, v, scale: Optional[float] = None,
     fused qkv projection does); one that does not raises RuntimeError.
 
     Cost statement for what still pads. Other 16-bit head dims under 128
-    (48, 72, 88, 96, ...), and 40 / 80 with block_mask=, in
+    (48, 72, 88, 96, ...), and 40 / 80 with block_mask= or row_bounds=, in
     attention_bshd_split and in the _lse ops, are zero-padded up to 64 / 128
     on this op: padding q/k leaves every softmax score unchanged, padded v
     columns are sliced off the output. That wastes attention FLOPs in
@@ -738,14 +859,18 @@ def attention_bshd(q, k, v, scale: Optional[float] = None,
     need a 256-class tile that does not exist: they take the reference path
     with a warning.
     """
-    return _attention(q, k, v, scale, key_mask, block_mask, bshd=True)
+    return _attention(q, k, v, scale, key_mask, block_mask, bshd=True,
+                      row_bounds=row_bounds)
 
 
 def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None,
-                         key_mask=None, block_mask=None):
+                         key_mask=None, block_mask=None, row_bounds=None):
     """attention_bshd with per-stream outputs: rows [:split] and [split:]
     land in two contiguous tensors (feeds dual-stream projections with no
-    reshape copies). key_mask and block_mask as in attention_bshd."""
+    reshape copies). key_mask and block_mask as in attention_bshd;
+    row_bounds= raises ValueError: not supported here."""
+    if row_bounds is not None:
+        raise ValueError(_NO_ROW_BOUNDS.format("attention_bshd_split"))
     return _attention(q, k, v, scale, key_mask, block_mask, bshd=True,
                       split=split)
 
@@ -756,7 +881,7 @@ _NO_BLOCK_LSE = ("block masks are not supported together with the "
 
 
 def attention_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
-                  block_mask=None):
+                  block_mask=None, row_bounds=None):
     """attention that also returns the log-sum-exp: (out [B, H, Sq, D], fp32
     lse [B, H, Sq]), lse = log of the sum over the row's visible keys of
     exp(scale * q.k). Partial results over disjoint key sets combine exactly
@@ -764,18 +889,22 @@ def attention_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
 
     Arguments, refusals and empties as in attention; a row that sees no key
     (Sk = 0, a batch element with no live key) has out = 0 and lse = -inf.
-    block_mask= raises ValueError: block masks with the lse are not
-    supported."""
+    block_mask= and row_bounds= raise ValueError: neither is supported with
+    the lse."""
+    if row_bounds is not None:
+        raise ValueError(_NO_ROW_BOUNDS.format("attention_lse"))
     if block_mask is not None:
         raise ValueError(f"attention_lse: {_NO_BLOCK_LSE}")
     return _attention(q, k, v, scale, key_mask, None, bshd=False, lse=True)
 
 
 def attention_bshd_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
-                       block_mask=None):
+                       block_mask=None, row_bounds=None):
     """attention_bshd that also returns the log-sum-exp: (out [B, Sq, H, D],
     fp32 lse [B, Sq, H]); see attention_lse. Strided views and head dims
     under 128 work as in attention_bshd."""
+    if row_bounds is not None:
+        raise ValueError(_NO_ROW_BOUNDS.format("attention_bshd_lse"))
     if block_mask is not None:
         raise ValueError(f"attention_bshd_lse: {_NO_BLOCK_LSE}")
     return _attention(q, k, v, scale, key_mask, None, bshd=True, lse=True)

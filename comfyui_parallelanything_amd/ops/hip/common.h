@@ -100,6 +100,29 @@ PA_DEV float block_reduce_sum(float v, float* scratch) {
     return total;
 }
 
+// The same pair for an integer minimum (a maximum is the minimum of the
+// negated values): exact at any magnitude, which a float reduction is not.
+PA_DEV int wave_reduce_min(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+template <int BLOCK>
+PA_DEV int block_reduce_min(int v, int* scratch) {
+    constexpr int NW = BLOCK / WAVE;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wid = threadIdx.x / WAVE;
+    v = wave_reduce_min(v);
+    __syncthreads();  // protect scratch against the previous reduction's reads
+    if (lane == 0) scratch[wid] = v;
+    __syncthreads();
+    int total = scratch[0];
+#pragma unroll
+    for (int i = 1; i < NW; ++i) total = min(total, scratch[i]);
+    return total;
+}
+
 // ---------------------------------------------------------------------------
 // Host side: argument checks, current stream, dtype binding.
 // ---------------------------------------------------------------------------

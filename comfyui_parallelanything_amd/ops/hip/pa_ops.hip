@@ -68,6 +68,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("pack_block_lists", &pack_block_lists,
           "[nq,nk] block mask + key-mask words -> per-(b, q-block) live "
           "tile lists [B,nq,nk] and counts [B,nq]");
+    m.def("pack_row_bounds", &pack_row_bounds,
+          "[Sq] integer row bounds lo, hi -> (clamped lo_c, hi_c, per-query-"
+          "block tile range [nq,4])",
+          py::arg("lo"), py::arg("hi"), py::arg("Sk"));
+    m.def("attn_fwd_band", &attn_fwd_band,
+          "attn_fwd with packed row bounds: row i sees keys [lo[i], hi[i])");
+    m.def("attn_fwd_bshd_band", &attn_fwd_bshd_band,
+          "attn_fwd_bshd with packed row bounds");
     m.def("attn_fwd_masked", &attn_fwd_masked,
           "attn_fwd with a packed key-padding mask (dead tiles skipped)");
     m.def("attn_fwd_bshd_masked", &attn_fwd_bshd_masked,

@@ -256,6 +256,36 @@ def as_bool_block_mask(mask: torch.Tensor, Sq: int, Sk: int) -> torch.Tensor:
     return mask if mask.dtype == torch.bool else mask != 0
 
 
+def check_row_bounds(lo, hi, Sq: int):
+    """lo, hi: two [Sq] integer tensors (query row i sees the keys lo[i] <=
+    j < hi[i]). Floating and bool tensors are refused for as_bool_key_mask's
+    reason: nothing is guessed from a mask or a bias. Another rank or length
+    raises ValueError."""
+    for name, t in (("lo", lo), ("hi", hi)):
+        if (t.dtype.is_floating_point or t.dtype.is_complex
+                or t.dtype == torch.bool):
+            raise ValueError(
+                f"row bounds must be integer key indices, got {name} of "
+                f"{t.dtype}: masks and additive float biases are not "
+                f"supported here")
+        if t.dim() != 1 or t.shape[0] != Sq:
+            raise ValueError(f"row bounds must be two [Sq] = [{Sq}] tensors, "
+                             f"got {name} {list(t.shape)}")
+    if lo.device != hi.device:
+        raise ValueError(f"row bounds: lo on {lo.device}, hi on {hi.device}")
+
+
+def as_row_bounds(row_bounds, Sq: int, Sk: int):
+    """(lo, hi) checked -> the pair as int64, clamped to [0, Sk]."""
+    lo, hi = row_bounds
+    check_row_bounds(lo, hi, Sq)
+    return lo.long().clamp(0, Sk), hi.long().clamp(0, Sk)
+
+
+NO_ROW_BOUNDS_WITH_MASK = ("row_bounds= together with key_mask= or "
+                           "block_mask= is not supported")
+
+
 def check_qkv(q, k, v, bshd: bool = False, split: Optional[int] = None):
     """k and v must have q's batch, head count and head dim, and one length
     between them; ``split`` lies inside (0, Sq). The native kernel indexes k
@@ -286,6 +316,7 @@ def attention(
     key_mask: Optional[torch.Tensor] = None,
     block_mask: Optional[torch.Tensor] = None,
     return_lse: bool = False,
+    row_bounds=None,
 ):
     """Plain attention, [B, H, S, D] -> [B, H, S, D]. fp32 softmax.
 
@@ -307,10 +338,20 @@ def attention(
     (zeroed before the matmuls), and a query row with no visible key gives
     zeros.
 
+    row_bounds: optional (lo, hi), two [Sq] integer tensors shared by batch
+    and heads. Key j is visible to query row i iff lo[i] <= j < hi[i] and
+    j < Sk; the bounds are clamped to [0, Sk], and a row with lo >= hi after
+    clamping sees no key and gives zeros. Not supported together with
+    key_mask= or block_mask= (ValueError). K/V inside [0, Sk) must be
+    finite (see ops.pack_row_bounds).
+
     k and v have q's batch, head count and head dim (ValueError otherwise:
     nothing is broadcast, as on the native kernels). Sk = 0 gives zeros.
     """
     check_qkv(q, k, v)
+    if row_bounds is not None and not (key_mask is None
+                                       and block_mask is None):
+        raise ValueError(f"attention: {NO_ROW_BOUNDS_WITH_MASK}")
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     dtype = q.dtype
@@ -329,6 +370,11 @@ def attention(
                              f"[B={B}, Sk={Sk}]")
         m = m[:, None, None, :]                         # [B, 1, 1, Sk]
         vis = m if vis is None else vis & m
+    if row_bounds is not None:
+        lo, hi = (t.to(q.device)[:, None]
+                  for t in as_row_bounds(row_bounds, Sq, Sk))
+        j = torch.arange(Sk, device=q.device)[None, :]
+        vis = ((j >= lo) & (j < hi))[None, None]        # [1, 1, Sq, Sk]
     qf, kf, vf = _wide(q), _wide(k), _wide(v)
     if vis is not None:
         # Unmasked calls skip this: a copy of k or v can take matmul down

@@ -23,6 +23,12 @@ kernel's overhead against --key-mask full), frame:W = the frame window of
 ops.frame_window_block_mask (needs --frames). The mask density — live
 256x64 blocks over all blocks — is printed beside each time.
 
+--row-bounds {causal,frame:B,A} runs the row-bounds kernels instead (no key
+or block mask, no --lse): causal = ops.causal_row_bounds, frame:B,A = ops.
+frame_span_row_bounds over --frames (B may be `all`), packed once outside
+the timed loop. Printed beside each time: the fraction of (query block,
+tile) pairs the kernel visits, which times the dense time is the yardstick.
+
 The sd15_* rows are SD1.5's head dims (8 heads over 320 / 640 channels, and
 the 77-token cross-attention). They run as the UNet calls them: ops.
 attention_bshd on [B, S, H, D] tensors, then .flatten(2). --only NAMES keeps
@@ -104,6 +110,8 @@ def main():
     ap.add_argument("--live-keys", type=int, default=64,
                     help="live keys per batch element for --key-mask lens")
     ap.add_argument("--block-mask", default="none", metavar="none|full|frame:W")
+    ap.add_argument("--row-bounds", default="none",
+                    metavar="none|causal|frame:B,A")
     ap.add_argument("--frames", type=int, default=0,
                     help="run the WAN 720p shape with this many latent "
                          "frames (3600 tokens each) instead of the table")
@@ -128,6 +136,17 @@ def main():
             ap.error("--block-mask frame:W needs --frames")
     elif args.block_mask not in ("none", "full"):
         ap.error("--block-mask takes none, full or frame:W")
+    span = None
+    if args.row_bounds.startswith("frame:"):
+        back, ahead = args.row_bounds.split(":", 1)[1].split(",")
+        span = (None if back == "all" else int(back), int(ahead))
+        if args.frames <= 0:
+            ap.error("--row-bounds frame:B,A needs --frames")
+    elif args.row_bounds not in ("none", "causal"):
+        ap.error("--row-bounds takes none, causal or frame:B,A")
+    if args.row_bounds != "none" and (
+            args.lse or args.key_mask != "none" or args.block_mask != "none"):
+        ap.error("--row-bounds takes no --lse, key mask or block mask")
     dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
     assert torch.cuda.is_available()
     dev = "cuda"
@@ -137,7 +156,8 @@ def main():
         return
     attn = ops.attention_lse if args.lse else ops.attention
     print(f"== attention{' + lse' if args.lse else ''} ({args.dtype}, random data, "
-          f"key mask: {args.key_mask}, block mask: {args.block_mask}) ==")
+          f"key mask: {args.key_mask}, block mask: {args.block_mask}, "
+          f"row bounds: {args.row_bounds}) ==")
     tokens_per_frame = 3600  # 720p: (720/16) x (1280/16) latent patches
     video = {f"wan720p_f{args.frames}": (
         1, 40, args.frames * tokens_per_frame,
@@ -163,8 +183,10 @@ def main():
         table = {n: table[n] for n in names}
     for name, (B, H, S, Sk, D) in table.items():
         bshd = name.startswith("sd15_")
-        if bshd and (args.lse or args.block_mask != "none"):
-            ap.error(f"{name} runs attention_bshd: no --lse, no block mask")
+        if bshd and (args.lse or args.block_mask != "none"
+                     or args.row_bounds != "none"):
+            ap.error(f"{name} runs attention_bshd: no --lse, no block mask, "
+                     f"no row bounds")
         q = torch.randn(B, H, S, D, device=dev, dtype=dtype)
         k = torch.randn(B, H, Sk, D, device=dev, dtype=dtype)
         v = torch.randn_like(k)
@@ -184,6 +206,15 @@ def main():
                          args.frames, tokens_per_frame, window, device=dev))
             mk = {"block_mask": ops.pack_block_mask(block, B, S, Sk, km)}
             note = f"  density {block.float().mean().item():.4f}"
+        if args.row_bounds != "none":
+            lo, hi = (ops.causal_row_bounds(S, Sk, device=dev)
+                      if span is None else ops.frame_span_row_bounds(
+                          args.frames, tokens_per_frame, *span, device=dev))
+            rb = ops.pack_row_bounds(lo, hi, S, Sk)
+            mk = {"row_bounds": rb}
+            rng = rb.range.cpu()
+            visited = (rng[:, 1] - rng[:, 0]).sum().item()
+            note = f"  visited {visited / (rng.shape[0] * ((Sk + 63) // 64)):.4f}"
         if bshd:
             dt = timeit(lambda: ops.attention_bshd(q, k, v, **mk).flatten(2),
                         iters=200, warmup=20)
