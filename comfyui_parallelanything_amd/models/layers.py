@@ -242,6 +242,46 @@ def joint_key_mask(attention_mask, B: int, txt_len: int, img_len: int):
     return ops.pack_key_mask(torch.cat([m, ones], dim=1))
 
 
+def joint_attn_mask(attn_mask, B: int, txt_len: int, img_len: int):
+    """Pack a dense mask over the joint txt|img sequence once per forward
+    (ops.pack_attn_mask: [S, S], [Bm, S, S] or [Bm, 1, S, S], S = txt_len +
+    img_len, nonzero = attend). None in, None out."""
+    if attn_mask is None:
+        return None
+    S = txt_len + img_len
+    return ops.pack_attn_mask(attn_mask, B, S, S)
+
+
+def regional_joint_mask(txt_len: int, h: int, w: int, regions):
+    """Dense bool mask [S, S], S = txt_len + h * w, for regional prompting on
+    the joint txt|img sequence (text first, image tokens row-major), to pass
+    as ``attn_mask=``. ``regions`` is a list of (txt_start, txt_end, map),
+    map a [h, w] bool tensor.
+
+    The definition: a text token of a span sees the text of its own span and
+    the image tokens of its map; an image token sees every image token and
+    the text spans of every region whose map holds it; text tokens in no
+    span see nothing and are seen by nothing (their rows come out zero).
+    Regions may overlap, in text and in image. The mask is built on the
+    device of the first map."""
+    S = txt_len + h * w
+    dev = regions[0][2].device if regions else None
+    mask = torch.zeros(S, S, dtype=torch.bool, device=dev)
+    mask[txt_len:, txt_len:] = True
+    for start, end, region in regions:
+        if not 0 <= start <= end <= txt_len:
+            raise ValueError(f"regional_joint_mask: text span [{start}, "
+                             f"{end}) outside [0, {txt_len}]")
+        if tuple(region.shape) != (h, w):
+            raise ValueError(f"regional_joint_mask: map must be [{h}, {w}], "
+                             f"got {list(region.shape)}")
+        inside = region.reshape(-1).to(device=dev, dtype=torch.bool)
+        mask[start:end, start:end] = True
+        mask[start:end, txt_len:] |= inside[None, :]
+        mask[txt_len:, start:end] |= inside[:, None]
+    return mask
+
+
 def context_key_mask(attention_mask, context):
     """Pack ``attention_mask`` ([B, T] over the context tokens) for the
     cross-attention of models whose keys are the context alone."""
@@ -295,8 +335,12 @@ class DoubleStreamBlock(nn.Module):
         )
         return q, k, v
 
-    def forward(self, img, txt, vec, pe, mods=None, key_mask=None):
-        # key_mask: optional ops.KeyMask over the joint txt|img keys
+    def forward(self, img, txt, vec, pe, mods=None, key_mask=None,
+                attn_mask=None):
+        # key_mask: optional ops.KeyMask over the joint txt|img keys;
+        # attn_mask: optional ops.AttnMask over the joint sequence (passed
+        # on only when set, so every other forward calls the op as before)
+        mk = {} if attn_mask is None else {"attn_mask": attn_mask}
         if mods is not None:
             (img_m1, img_m2), (txt_m1, txt_m2) = mods
         else:
@@ -322,7 +366,7 @@ class DoubleStreamBlock(nn.Module):
             pe,
         )
         txt_attn, img_attn = ops.attention_bshd_split(
-            q, k, v, T, self.attn.scale, key_mask=key_mask
+            q, k, v, T, self.attn.scale, key_mask=key_mask, **mk
         )
         txt_attn = txt_attn.flatten(2)
         img_attn = img_attn.flatten(2)
@@ -359,8 +403,11 @@ class SingleStreamBlock(nn.Module):
         self.modulation = Modulation(hidden, double=False)
         self.attn = JointAttention(num_heads, head_dim)
 
-    def forward(self, x, vec, pe, mods=None, key_mask=None):
-        # key_mask: optional ops.KeyMask over this sequence's keys
+    def forward(self, x, vec, pe, mods=None, key_mask=None, attn_mask=None):
+        # key_mask: optional ops.KeyMask over this sequence's keys;
+        # attn_mask: optional ops.AttnMask over the sequence (passed on only
+        # when set)
+        mk = {} if attn_mask is None else {"attn_mask": attn_mask}
         B, S, hidden = x.shape
         if mods is not None:
             (mod,) = mods
@@ -395,7 +442,7 @@ class SingleStreamBlock(nn.Module):
             q, k, self.norm.query_norm.scale, self.norm.key_norm.scale, pe
         )
         attn = ops.attention_bshd(q, k, v, self.attn.scale,
-                                  key_mask=key_mask).flatten(2)
+                                  key_mask=key_mask, **mk).flatten(2)
         if mlp_fp8 is not None:
             out = self.linear2_attn(attn) + self.linear2_mlp.mm_fp8(*mlp_fp8)
         elif x.is_cuda and isinstance(self.linear2_mlp, nn.Linear):

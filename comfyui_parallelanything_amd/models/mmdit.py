@@ -27,6 +27,7 @@ from .layers import (
     MLPEmbedder,
     ModulationBank,
     SingleStreamBlock,
+    joint_attn_mask,
     joint_key_mask,
     rope_2d_table,
 )
@@ -143,7 +144,10 @@ class Flux(nn.Module):
 
     @torch.no_grad()
     def forward(self, x, timesteps, context=None, y=None, guidance=None,
-                attention_mask=None, **kwargs):
+                attention_mask=None, attn_mask=None, **kwargs):
+        # attention_mask: [B, T] key-padding mask over the context tokens;
+        # attn_mask: dense mask over the joint txt|img sequence
+        # (ops.pack_attn_mask, layers.regional_joint_mask). One or the other.
         cfg = self.cfg
         B = x.shape[0]
         img, h, w = self._patchify(x)
@@ -182,6 +186,13 @@ class Flux(nn.Module):
         if attention_mask is not None:
             mk["key_mask"] = joint_key_mask(attention_mask, B, txt.shape[1],
                                             img.shape[1])
+        if attn_mask is not None:
+            if attention_mask is not None:
+                raise ValueError("attn_mask= together with attention_mask= "
+                                 "is not supported: fold the key padding "
+                                 "into the dense mask")
+            mk["attn_mask"] = joint_attn_mask(attn_mask, B, txt.shape[1],
+                                              img.shape[1])
 
         i = 0
         for block in self.double_blocks:
@@ -256,7 +267,8 @@ class ZImage(nn.Module):
 
     @torch.no_grad()
     def forward(self, x, timesteps, context=None, attention_mask=None,
-                **kwargs):
+                attn_mask=None, **kwargs):
+        # attention_mask / attn_mask as in MMDiT.forward
         cfg = self.cfg
         B, C, H, W = x.shape
         p = cfg.patch_size
@@ -285,6 +297,13 @@ class ZImage(nn.Module):
         if attention_mask is not None:
             mk["key_mask"] = joint_key_mask(attention_mask, B, txt.shape[1],
                                             img.shape[1])
+        if attn_mask is not None:
+            if attention_mask is not None:
+                raise ValueError("attn_mask= together with attention_mask= "
+                                 "is not supported: fold the key padding "
+                                 "into the dense mask")
+            mk["attn_mask"] = joint_attn_mask(attn_mask, B, txt.shape[1],
+                                              img.shape[1])
         for i, block in enumerate(self.layers):
             seq = block(seq, vec, pe,
                         mods=(banked[i][0],) if banked else None, **mk)

@@ -659,9 +659,104 @@ _NO_ROW_BOUNDS = ("row_bounds= is not supported in {} (attention and "
                   "attention_bshd take it)")
 
 
-def _mask_for(key_mask, block_mask, q, Sq: int, Sk: int, row_bounds=None):
+@dataclass
+class AttnMask:
+    """A dense attention mask packed for the dense-mask attention kernels:
+    query row i of batch element b sees an arbitrary set of keys, shared by
+    heads.
+
+    Tensors, plus the three integers the pack was made for (checked before
+    every launch; parallel.pipeline's recursive move carries the tensors
+    across devices and leaves the integers as they are). With nq =
+    ceil(Sq/256), nk = ceil(Sk/64) and Bm = 1 (shared by the batch) or batch:
+      mask   bool [Bm, Sq, Sk], True = attend
+      bits   [Bm, nk, Sq] int64: bit j of bits[bm][t][i] = mask[bm][i][64t+j]
+      words  [Bm, nq, nk] int64: OR of the block's rows' words, the K/V rows
+             the block stages
+      list   [Bm, nq, nk] int32: per (bm, query block) the ascending tiles
+             with a nonzero OR word, compacted, zero tail; bit 30 of an entry
+             is set when every row of the block sees the tile whole
+      nlist  [Bm, nq] int32
+    On CPU only ``mask`` is set. ``list`` drives the kernel's K/V loads, so
+    the pack kernels are its only producers: build one with pack_attn_mask,
+    never by hand (ops/hip/attention.h, pack_attn_mask_kernel).
+    """
+    mask: torch.Tensor
+    bits: Optional[torch.Tensor] = None
+    words: Optional[torch.Tensor] = None
+    list: Optional[torch.Tensor] = None
+    nlist: Optional[torch.Tensor] = None
+    batch: int = 0
+    Sq: int = 0
+    Sk: int = 0
+
+
+def pack_attn_mask(mask, batch: int, Sq: int, Sk: int) -> AttnMask:
+    """Pack a dense bool/integer attention mask (nonzero = attend) once, for
+    any number of attention calls of that batch size and those lengths:
+    [Sq, Sk], [Bm, Sq, Sk] or [Bm, 1, Sq, Sk] with Bm in {1, batch}, shared
+    by heads. What torch SDPA and ComfyUI's optimized_attention call a
+    boolean attn_mask.
+
+    Contract of every ``attn_mask=`` argument below: key j is visible to
+    query row i of batch element b iff mask[b or 0][i][j] != 0 and j < Sk. A
+    row with no visible key returns zeros exactly. A 256-row query block
+    loads only the K/V rows some row of it sees: K/V rows that no query row
+    of the batch element sees are don't-care (NaN included), every other K/V
+    row must be finite, because a key one row does not see still meets p = 0
+    where another row of its block sees it. Nothing is read on the host, so
+    pack + attention capture into one graph. Floating masks raise, as in
+    pack_key_mask; a head dimension other than 1 or another shape raises
+    ValueError. Not supported: together with key_mask=, block_mask= or
+    row_bounds=, in the _lse ops (ValueError each), per-head masks, additive
+    biases. Head dims 40 / 80 follow the block masks' rule (attention_bshd).
+
+    Cost: the bool mask is Sq * Sk bytes per batch element and the pack 1/8
+    of it (2.6 MB at S = 4608). A mask too large to hold as a dense bool
+    tensor (WAN's 75k tokens: 5.7 GB) is out of scope: use block_mask= or
+    row_bounds= there.
+    """
+    batch, Sq, Sk = int(batch), int(Sq), int(Sk)
+    m = reference.as_bool_attn_mask(mask, batch, Sq, Sk)
+    if m.is_cuda:
+        ext = _require_ext("pack_attn_mask")
+        if ext is not None:
+            return AttnMask(m, *ext.pack_attn_mask(m), batch, Sq, Sk)
+    return AttnMask(m, batch=batch, Sq=Sq, Sk=Sk)
+
+
+def _attn_mask_for(attn_mask, q, Sq: int, Sk: int) -> AttnMask:
+    B = q.shape[0]
+    am = attn_mask
+    if not isinstance(am, AttnMask):
+        am = pack_attn_mask(am, B, Sq, Sk)
+    elif (am.batch, am.Sq, am.Sk) != (B, Sq, Sk):
+        raise ValueError(
+            f"AttnMask was packed for (B, Sq, Sk) = "
+            f"{(am.batch, am.Sq, am.Sk)}, this call has {(B, Sq, Sk)}")
+    if am.mask.device != q.device:
+        raise ValueError(f"attn_mask on {am.mask.device}, q on {q.device}")
+    if q.is_cuda and am.bits is None:
+        # packed on CPU (or under PA_ALLOW_EAGER) and moved: pack here
+        am = pack_attn_mask(am.mask, B, Sq, Sk)
+    return am
+
+
+_NO_ATTN_MASK_LSE = ("attn_mask= is not supported together with the "
+                     "log-sum-exp output (attention_lse / attention_bshd_lse "
+                     "take key_mask= only)")
+
+
+def _mask_for(key_mask, block_mask, q, Sq: int, Sk: int, row_bounds=None,
+              attn_mask=None):
     """The call's packed mask: None, a KeyMask, a BlockMask (which holds
-    the key mask too) or a RowBounds."""
+    the key mask too), a RowBounds or an AttnMask."""
+    if attn_mask is not None:
+        if not (key_mask is None and block_mask is None
+                and row_bounds is None):
+            raise ValueError(
+                f"attention: {reference.NO_ATTN_MASK_WITH_MASK}")
+        return _attn_mask_for(attn_mask, q, Sq, Sk)
     if row_bounds is not None:
         if key_mask is not None or block_mask is not None:
             raise ValueError(
@@ -678,6 +773,8 @@ def _mask_kw(km) -> dict:
         return {"key_mask": km.keys, "block_mask": km.block}
     if isinstance(km, RowBounds):
         return {"row_bounds": (km.lo, km.hi)}
+    if isinstance(km, AttnMask):
+        return {"attn_mask": km.mask}
     return {"key_mask": None if km is None else km.mask}
 
 
@@ -703,7 +800,7 @@ _check_qkv = reference.check_qkv
 
 def _attn_op(bshd: bool, split=None, lse: bool = False) -> str:
     """attn_fwd[_bshd][_split][_lse]: the op as _unsupported names it, and
-    the extension's binding up to its _masked / _band suffix."""
+    the extension's binding up to its _masked / _band / _bits suffix."""
     return ("attn_fwd" + ("_bshd" if bshd else "")
             + ("_split" if split is not None else "")
             + ("_lse" if lse else ""))
@@ -715,13 +812,13 @@ def _attn_head_dim(ext, q, km, bshd: bool, split=None, lse: bool = False):
     for the other head dims of the extension's table (40, 80) on plain and
     key-masked calls; 64 or 128, to zero-pad to, for what is left of the
     16-bit head dims under 128 on the un-split BSHD ops (see attention_bshd);
-    None when the call is not covered. Row bounds follow the block masks'
-    rule: 40 and 80 are padded."""
+    None when the call is not covered. Row bounds and dense masks follow the
+    block masks' rule: 40 and 80 are padded."""
     D = q.shape[-1]
     if q.dtype not in _NATIVE16:
         return None
     plain = (split is None and not lse
-             and not isinstance(km, (BlockMask, RowBounds)))
+             and not isinstance(km, (BlockMask, RowBounds, AttnMask)))
     if D in (64, 128) or (plain and D in ext.attn_native_head_dims()):
         return D
     if D < 128 and bshd and split is None:
@@ -738,11 +835,12 @@ def _attn_native(q, k, v, scale: float, km, bshd: bool,
 
     Picks ext.attn_fwd[_bshd][_split][_lse][_masked]; ``km`` is None, a
     KeyMask, a BlockMask, whose 3-D ``live`` selects the block-list
-    kernels inside the masked entry points, or a RowBounds, which has the
-    _band entry points."""
-    band = isinstance(km, RowBounds)
+    kernels inside the masked entry points, a RowBounds, which has the
+    _band entry points, or an AttnMask, which has the _bits ones."""
+    band, bits = isinstance(km, RowBounds), isinstance(km, AttnMask)
     name = _attn_op(bshd, split, lse) + (
-        "_band" if band else "_masked" if km is not None else "")
+        "_band" if band else "_bits" if bits
+        else "_masked" if km is not None else "")
     ext = _require_ext(name)
     if ext is None:
         return None, None
@@ -755,6 +853,8 @@ def _attn_native(q, k, v, scale: float, km, bshd: bool,
         args += (int(split),)
     if band:
         args += (km.lo_c, km.hi_c, km.range)
+    elif bits:
+        args += (km.bits, km.words, km.list, km.nlist)
     elif km is not None:
         args += (km.words, km.live, km.nlive)
     if width != D:
@@ -772,12 +872,12 @@ def _attn_native(q, k, v, scale: float, km, bshd: bool,
 
 def _attention(q, k, v, scale, key_mask, block_mask, *, bshd: bool,
                split: Optional[int] = None, lse: bool = False,
-               row_bounds=None):
+               row_bounds=None, attn_mask=None):
     """The body of the five public ops: check, pack the mask, run the native
     kernels, else note the gap and take the reference path."""
     Sq, Sk = _check_qkv(q, k, v, bshd=bshd, split=split)
     scale = _softmax_scale(q, scale)
-    km = _mask_for(key_mask, block_mask, q, Sq, Sk, row_bounds)
+    km = _mask_for(key_mask, block_mask, q, Sq, Sk, row_bounds, attn_mask)
     why = None
     if q.is_cuda:
         res, why = _attn_native(q, k, v, scale, km, bshd, split, lse)
@@ -791,8 +891,12 @@ def _attention(q, k, v, scale, key_mask, block_mask, *, bshd: bool,
         if (why is not None and km is None
                 and _attn_head_dim(hip_ext(), q, km, bshd) is None):
             _unsupported(_attn_op(bshd, split), why)
-        packed = (None, km) if isinstance(km, BlockMask) else (km, None)
-        out = _attention(q, k, v, scale, *packed, bshd=bshd)
+        if isinstance(km, AttnMask):
+            out = _attention(q, k, v, scale, None, None, bshd=bshd,
+                             attn_mask=km)
+        else:
+            packed = (None, km) if isinstance(km, BlockMask) else (km, None)
+            out = _attention(q, k, v, scale, *packed, bshd=bshd)
         return out[:, :split].contiguous(), out[:, split:].contiguous()
     if why is not None:
         _unsupported(_attn_op(bshd, lse=lse), why)
@@ -807,7 +911,8 @@ def _attention(q, k, v, scale, key_mask, block_mask, *, bshd: bool,
 
 
 def attention(q, k, v, scale: Optional[float] = None,
-              key_mask=None, block_mask=None, row_bounds=None) -> torch.Tensor:
+              key_mask=None, block_mask=None, row_bounds=None,
+              attn_mask=None) -> torch.Tensor:
     """Flash-style fused attention, layout [B, H, S, D].
 
     key_mask: optional KeyMask or raw [B, Sk] bool/integer mask (see
@@ -821,24 +926,30 @@ def attention(q, k, v, scale: Optional[float] = None,
     pack_row_bounds for the contract; causal_row_bounds and
     frame_span_row_bounds build the usual ones). A raw pair is packed per
     call. Together with key_mask= or block_mask= it raises ValueError.
+    attn_mask: optional AttnMask or raw dense bool/integer mask, [Sq, Sk],
+    [Bm, Sq, Sk] or [Bm, 1, Sq, Sk] with Bm in {1, B}: query row i of batch
+    element b sees the keys j with mask[b or 0][i][j] != 0 (see
+    pack_attn_mask for the contract and the memory cost). A raw one is
+    packed per call. Together with any other mask it raises ValueError.
 
     k and v have q's batch, head count and head dim and one length Sk;
     anything else raises ValueError (nothing is broadcast). B, H or Sq of
     zero returns the empty result, Sk = 0 zeros: no row sees a key."""
     return _attention(q, k, v, scale, key_mask, block_mask, bshd=False,
-                      row_bounds=row_bounds)
+                      row_bounds=row_bounds, attn_mask=attn_mask)
 
 
 def attention_bshd(q, k, v, scale: Optional[float] = None,
                    key_mask=None, block_mask=None,
-                   row_bounds=None) -> torch.Tensor:
+                   row_bounds=None, attn_mask=None) -> torch.Tensor:
     """Fused attention on [B, S, H, D] (strided views allowed — e.g. slices
     of a fused qkv projection; no transpose/contiguous copies on GPU).
 
     key_mask: optional KeyMask or raw [B, Sk] bool/integer mask (see
     pack_key_mask for the contract). block_mask: optional BlockMask or raw
     [ceil(Sq/256), ceil(Sk/64)] mask, row_bounds: optional RowBounds or raw
-    (lo, hi) pair, both as in attention.
+    (lo, hi) pair, attn_mask: optional AttnMask or raw dense mask, all as in
+    attention.
 
     Head dims. 64 and 128 are the kernel's two tile classes. SD1.5's 40 and
     80 have kernels of their own inside those classes (docs/KERNELS.md,
@@ -848,7 +959,8 @@ def attention_bshd(q, k, v, scale: Optional[float] = None,
     fused qkv projection does); one that does not raises RuntimeError.
 
     Cost statement for what still pads. Other 16-bit head dims under 128
-    (48, 72, 88, 96, ...), and 40 / 80 with block_mask= or row_bounds=, in
+    (48, 72, 88, 96, ...), and 40 / 80 with block_mask=, row_bounds= or
+    attn_mask=, in
     attention_bshd_split and in the _lse ops, are zero-padded up to 64 / 128
     on this op: padding q/k leaves every softmax score unchanged, padded v
     columns are sliced off the output. That wastes attention FLOPs in
@@ -860,19 +972,20 @@ def attention_bshd(q, k, v, scale: Optional[float] = None,
     with a warning.
     """
     return _attention(q, k, v, scale, key_mask, block_mask, bshd=True,
-                      row_bounds=row_bounds)
+                      row_bounds=row_bounds, attn_mask=attn_mask)
 
 
 def attention_bshd_split(q, k, v, split: int, scale: Optional[float] = None,
-                         key_mask=None, block_mask=None, row_bounds=None):
+                         key_mask=None, block_mask=None, row_bounds=None,
+                         attn_mask=None):
     """attention_bshd with per-stream outputs: rows [:split] and [split:]
     land in two contiguous tensors (feeds dual-stream projections with no
-    reshape copies). key_mask and block_mask as in attention_bshd;
-    row_bounds= raises ValueError: not supported here."""
+    reshape copies). key_mask, block_mask and attn_mask as in
+    attention_bshd; row_bounds= raises ValueError: not supported here."""
     if row_bounds is not None:
         raise ValueError(_NO_ROW_BOUNDS.format("attention_bshd_split"))
     return _attention(q, k, v, scale, key_mask, block_mask, bshd=True,
-                      split=split)
+                      split=split, attn_mask=attn_mask)
 
 
 _NO_BLOCK_LSE = ("block masks are not supported together with the "
@@ -881,7 +994,7 @@ _NO_BLOCK_LSE = ("block masks are not supported together with the "
 
 
 def attention_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
-                  block_mask=None, row_bounds=None):
+                  block_mask=None, row_bounds=None, attn_mask=None):
     """attention that also returns the log-sum-exp: (out [B, H, Sq, D], fp32
     lse [B, H, Sq]), lse = log of the sum over the row's visible keys of
     exp(scale * q.k). Partial results over disjoint key sets combine exactly
@@ -889,8 +1002,10 @@ def attention_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
 
     Arguments, refusals and empties as in attention; a row that sees no key
     (Sk = 0, a batch element with no live key) has out = 0 and lse = -inf.
-    block_mask= and row_bounds= raise ValueError: neither is supported with
-    the lse."""
+    block_mask=, row_bounds= and attn_mask= raise ValueError: none is
+    supported with the lse."""
+    if attn_mask is not None:
+        raise ValueError(f"attention_lse: {_NO_ATTN_MASK_LSE}")
     if row_bounds is not None:
         raise ValueError(_NO_ROW_BOUNDS.format("attention_lse"))
     if block_mask is not None:
@@ -899,10 +1014,12 @@ def attention_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
 
 
 def attention_bshd_lse(q, k, v, scale: Optional[float] = None, key_mask=None,
-                       block_mask=None, row_bounds=None):
+                       block_mask=None, row_bounds=None, attn_mask=None):
     """attention_bshd that also returns the log-sum-exp: (out [B, Sq, H, D],
     fp32 lse [B, Sq, H]); see attention_lse. Strided views and head dims
     under 128 work as in attention_bshd."""
+    if attn_mask is not None:
+        raise ValueError(f"attention_bshd_lse: {_NO_ATTN_MASK_LSE}")
     if row_bounds is not None:
         raise ValueError(_NO_ROW_BOUNDS.format("attention_bshd_lse"))
     if block_mask is not None:

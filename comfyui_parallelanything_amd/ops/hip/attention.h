@@ -1,5 +1,5 @@
-// Fused attention forward: key-mask, block-mask and row-bounds packs, the v4
-// kernel, the one launcher and the twelve entry points.
+// Fused attention forward: key-mask, block-mask, row-bounds and dense-mask
+// packs, the v4 kernel, the one launcher and the fifteen entry points.
 #pragma once
 
 using bf16x8 = short8;
@@ -282,6 +282,138 @@ std::vector<at::Tensor> pack_row_bounds(at::Tensor lo, at::Tensor hi,
 }
 
 // ---------------------------------------------------------------------------
+// Dense-mask pack: [Bm, Sq, Sk] bool (nonzero = query row i of batch element
+// bm attends key j) -> what the BITS attention instantiations read. With
+// nq = ceil(Sq/256) query blocks and nk = ceil(Sk/64) tiles:
+//   bits[bm][t][i]    bit j = mask[bm][i][64*t + j]; bits at or beyond Sk are
+//                     0. Tile-major, row-minor: the 32 rows of a wave are 256
+//                     contiguous bytes of one tile.
+//   words[bm][qb][t]  OR of bits[bm][t][i] over the block's rows i < Sq: the
+//                     K/V rows the block stages
+//   list[bm][qb][..]  ascending tiles t with words[bm][qb][t] != 0, compacted
+//                     to the front (zero tail); an entry is t | PA_BITS_FULL
+//                     when every row i < Sq of the block has all 64 bits of
+//                     the tile set (so the tail tile of an Sk % 64 != 0 call
+//                     is never full), t alone otherwise
+//   nlist[bm][qb]     how many
+// Two kernels, nothing read on the host (graph-capturable ahead of the
+// attention launch on the same stream).
+//
+// pack_attn_mask_kernel: one 256-thread block per (tile, query block, bm).
+// Wave w owns rows 256 qb + 64 w + (0..63); per step it ballots the 64 keys
+// of one row (a coalesced 64-byte read at any Sk and any alignment) and lane
+// s keeps the word of step s, so the wave ends with one word per lane and
+// stores 512 contiguous bytes. The ballot is wave-uniform: its OR and AND
+// over the rows accumulate in scalars as the steps go, and LDS combines the
+// four waves.
+// pack_attn_lists_kernel: one wave per (query block, bm), 64 tiles per step
+// with the ballot + prefix popcount of pack_block_lists_kernel.
+// ---------------------------------------------------------------------------
+constexpr int PA_BITS_FULL = 1 << 30;
+
+__global__ __launch_bounds__(256) void pack_attn_mask_kernel(
+    const unsigned char* __restrict__ mask,
+    unsigned long long* __restrict__ bits,
+    unsigned long long* __restrict__ words, int* __restrict__ full,
+    int Sq, int Sk, int n_tiles) {
+    __shared__ unsigned long long s_or[4], s_and[4];
+    const int t = blockIdx.x, qb = blockIdx.y, bm = blockIdx.z;
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    const int row0 = qb * 256 + wid * 64;
+    const int rows = min(64, Sq - row0);     // <= 0: this wave has no row
+    const int key = t * 64 + lane;
+    const unsigned char* mp = mask + ((long)bm * Sq + row0) * Sk + key;
+    unsigned long long mine = 0ull, w_or = 0ull, w_and = ~0ull;
+#pragma unroll 4
+    for (int s = 0; s < rows; ++s) {
+        const bool on = key < Sk && mp[(long)s * Sk] != 0;
+        const unsigned long long w = __ballot(on);
+        if (s == lane) mine = w;
+        w_or |= w;
+        w_and &= w;
+    }
+    if (lane < rows)
+        bits[((long)bm * n_tiles + t) * Sq + row0 + lane] = mine;
+    if (lane == 0) {
+        s_or[wid] = w_or;
+        s_and[wid] = w_and;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const long at = ((long)bm * gridDim.y + qb) * n_tiles + t;
+        words[at] = s_or[0] | s_or[1] | s_or[2] | s_or[3];
+        full[at] = (s_and[0] & s_and[1] & s_and[2] & s_and[3]) == ~0ull;
+    }
+}
+
+__global__ __launch_bounds__(64) void pack_attn_lists_kernel(
+    const unsigned long long* __restrict__ words,
+    const int* __restrict__ full, int* __restrict__ list,
+    int* __restrict__ nlist, int n_tiles) {
+    const long row = (long)blockIdx.y * gridDim.x + blockIdx.x;  // bm, qb
+    const int lane = threadIdx.x;
+    const unsigned long long* wb = words + row * n_tiles;
+    const int* fb = full + row * n_tiles;
+    int* lb = list + row * n_tiles;
+    int count = 0;
+    for (int base = 0; base < n_tiles; base += 64) {
+        const int t = base + lane;
+        const bool alive = t < n_tiles && wb[t] != 0ull;
+        const unsigned long long m = __ballot(alive);
+        if (alive)
+            lb[count + __popcll(m & ((1ull << lane) - 1ull))] =
+                t | (fb[t] != 0 ? PA_BITS_FULL : 0);
+        count += __popcll(m);
+    }
+    for (int i = count + lane; i < n_tiles; i += 64) lb[i] = 0;
+    if (lane == 0) nlist[row] = count;
+}
+
+// mask: [Bm, Sq, Sk] bool/integer -> {bits, words, list, nlist}.
+std::vector<at::Tensor> pack_attn_mask(at::Tensor mask) {
+    CHECK_GPU(mask);
+    TORCH_CHECK(mask.dim() == 3, "pack_attn_mask expects a [Bm, Sq, Sk] mask");
+    TORCH_CHECK(mask.scalar_type() == at::kBool ||
+                    at::isIntegralType(mask.scalar_type(), false),
+                "pack_attn_mask: bool or integer mask only (nonzero = "
+                "attend); additive float biases are not supported, got ",
+                mask.scalar_type());
+    TORCH_CHECK(mask.size(1) <= 0x7fffffffl && mask.size(2) <= 0x7fffffffl,
+                "pack_attn_mask: Sq and Sk must fit 31 bits");
+    auto mb = (mask.scalar_type() == at::kBool ? mask : mask.ne(0))
+                  .contiguous();
+    const int Bm = (int)mb.size(0), Sq = (int)mb.size(1),
+              Sk = (int)mb.size(2);
+    const int nq = (Sq + 255) / 256, n_tiles = (Sk + 63) / 64;
+    TORCH_CHECK(Bm <= 65535 && nq <= 65535,
+                "pack_attn_mask: batch ", Bm, " or query blocks ", nq,
+                " exceed 65535");
+    const auto ints = mb.options().dtype(at::kInt);
+    auto bits = at::empty({Bm, n_tiles, Sq}, mb.options().dtype(at::kLong));
+    auto words = at::empty({Bm, nq, n_tiles}, mb.options().dtype(at::kLong));
+    auto full = at::empty({Bm, nq, n_tiles}, ints);
+    auto list = at::empty({Bm, nq, n_tiles}, ints);
+    auto nlist = at::empty({Bm, nq}, ints);
+    if (Bm > 0 && nq > 0 && n_tiles > 0)
+        hipLaunchKernelGGL(pack_attn_mask_kernel,
+                           dim3((unsigned)n_tiles, (unsigned)nq, (unsigned)Bm),
+                           dim3(256), 0, cur_stream(),
+                           (const unsigned char*)mb.data_ptr(),
+                           (unsigned long long*)bits.data_ptr(),
+                           (unsigned long long*)words.data_ptr(),
+                           full.data_ptr<int>(), Sq, Sk, n_tiles);
+    if (Bm > 0 && nq > 0)
+        hipLaunchKernelGGL(pack_attn_lists_kernel,
+                           dim3((unsigned)nq, (unsigned)Bm), dim3(64), 0,
+                           cur_stream(),
+                           (const unsigned long long*)words.data_ptr(),
+                           full.data_ptr<int>(), list.data_ptr<int>(),
+                           nlist.data_ptr<int>(), n_tiles);
+    return {bits, words, list, nlist};
+}
+
+// ---------------------------------------------------------------------------
 // Attention v4: swapped-QK^T 32x32 structure (guide Appendix B ladder).
 //
 // mfma_f32_32x32x16_bf16 computing S^T = K·Q^T, so each LANE owns a full
@@ -371,8 +503,28 @@ std::vector<at::Tensor> pack_row_bounds(at::Tensor lo, at::Tensor hi,
 // and take the opaque scalar products of the DH < D flavour, so they round
 // as the class kernels do; every instantiation without the flag compiles to
 // the code it had before the flag existed.
+//
+// BITS (dense masks, see pack_attn_mask_kernel; plain flavour only): query
+// row i of batch element b sees key j iff its bit is set, an arbitrary set
+// per row. The three mask pointers carry the pack's per-(bm, query block)
+// tensors: mask_words the OR words, mask_live the tile list, mask_nlive its
+// length; bits_bstride is 1, or 0 for a mask shared by the batch (Bm = 1).
+// The KV loop walks the block's list as QLIST does, one readfirstlane per
+// tile: the entry is the tile index (held inside [0, n_tiles) here, so no
+// K/V address depends on what the list holds) plus the PA_BITS_FULL flag.
+// K/V rows are staged from the block's OR word exactly as MASKED stages from
+// its word, so a K/V row no query row of the block sees is never loaded. A
+// full tile branches over the substitution; any other tests the lane's own
+// 64-bit row word (each lane owns one query row) at the constant bit
+// positions of MASKED after the one shift by 4 hi. That word is loaded with
+// the K/V register prefetch of its tile, one or two tiles ahead of the
+// softmax that reads it, and rotates through named registers (rw_cur,
+// rw_next), so no load sits in the max -> exp2 -> sum chain. As under BAND a
+// processed tile may hold no live key for a row, so dead scores are -inf
+// over the mx = -3e30 floor, and the instantiations are built and rounded
+// the way BAND's are.
 template <int D, typename E, bool MASKED = false, bool QLIST = false,
-          bool LSE = false, int DH = D, bool BAND = false>
+          bool LSE = false, int DH = D, bool BAND = false, bool BITS = false>
 __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     const E* __restrict__ q, const E* __restrict__ k,
     const E* __restrict__ v, E* __restrict__ out,
@@ -390,7 +542,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     long l_bs = 0, long l_hs = 0, long l_ss = 0,
     const int* __restrict__ band_lo = nullptr,
     const int* __restrict__ band_hi = nullptr,
-    const int* __restrict__ band_range = nullptr) {
+    const int* __restrict__ band_range = nullptr,
+    const unsigned long long* __restrict__ row_bits = nullptr,
+    int bits_bstride = 0) {
     using EL = Elem16<E>;
     constexpr int KVBLK = 64;
     constexpr int WAVES = 8;
@@ -400,6 +554,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     static_assert(DH % 8 == 0 && DH > 0 && DH <= D, "head dim vs tile class");
     static_assert(!BAND || (!MASKED && !QLIST && !LSE && DH == D),
                   "row bounds: plain flavour of the two tile classes only");
+    static_assert(!BITS || (!MASKED && !QLIST && !LSE && DH == D && !BAND),
+                  "dense masks: plain flavour of the two tile classes only");
     constexpr int KK = (DH + 15) / 16;   // QK^T K-steps per 32-key tile
     constexpr int NV = (DH + 31) / 32;   // PV dim tiles
     constexpr int GROW = DH / 8;         // 16-byte granules per K/V row
@@ -443,7 +599,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     // BAND: the last query blocks launch first. Under causal and frame-causal
     // bounds they walk the most tiles, and the grid then ends on its shortest
     // blocks instead of its longest (docs/KERNELS.md "Row bounds", Speed).
-    if constexpr (BAND)
+    // BITS takes the same order: a causal mask is its commonest uneven one,
+    // and an even one does not care.
+    if constexpr (BAND || BITS)
         qtile = (S + WAVES * 32 - 1) / (WAVES * 32) - 1 - qtile;
     const long b = bh / H;
     const int h = (int)(bh % H);
@@ -507,7 +665,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     }
 
     bf16x8 kreg[KVECS], vreg[KVECS];
-    // `word` (MASKED only) is the tile's mask word: bit `row` set = stage
+    // `word` (MASKED, BITS) is the tile's mask word: bit `row` set = stage
     // the row, clear = stage zeros (covers src >= Sk, whose bits are 0)
     auto issue_tile_loads = [&](int kv0, unsigned long long word = 0) PA_INL {
 #pragma unroll
@@ -521,7 +679,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
             // stays in range, and nothing is staged there whatever bit or
             // key that row would name
             constexpr int RMASK = STAGE_TAIL ? 63 : -1;
-            if constexpr (MASKED)
+            if constexpr (MASKED || BITS)
                 stage = ((word >> (row & RMASK)) & 1ull) != 0;
             else stage = src < Sk;
             if constexpr (STAGE_TAIL)
@@ -583,7 +741,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
         __builtin_amdgcn_s_setprio(0);
     };
     auto softmax_phase = [&](int kv0, f32x16* st, bf16x8* pfrag,
-                             unsigned long long word = 0) PA_INL {
+                             unsigned long long word = 0,
+                             bool bits_full = false) PA_INL {
         // lane-local online softmax (this lane's row = q0 + l32);
         // value (kt, reg) = S[row][key = kt*32 + (reg&3) + 8*(reg>>2) + 4*hi]
         // raw tile max (scale2 > 0 commutes with max), softmax scale fused
@@ -597,8 +756,11 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
         // substitution works in place ahead of ONE softmax body: a second,
         // compile-time-full copy of the body costs registers (D=128 spills,
         // D=64 loses a resident block; scripts/attn_v6.hip v4/v5).
+        // BITS: `word` is this lane's row word, a VGPR pair, and `full` the
+        // list entry's flag.
         bool full;
         if constexpr (MASKED) full = word == ~0ull;
+        else if constexpr (BITS) full = bits_full;
         else if constexpr (BAND)
             full = band_f0k <= kv0 && kv0 < band_f1k && kv0 + KVBLK <= Sk;
         else full = kv0 + KVBLK <= Sk;
@@ -607,7 +769,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
             // the word's half kt — one 64-bit shift, then constant bit
             // positions
             unsigned int wh[2] = {0u, 0u};
-            if constexpr (MASKED) {
+            if constexpr (MASKED || BITS) {
                 const unsigned long long wl = word >> (4 * hi);
                 wh[0] = (unsigned int)wl;
                 wh[1] = (unsigned int)(wl >> 32);
@@ -619,16 +781,16 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
                     const int key =
                         kv0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
                     bool valid;
-                    if constexpr (MASKED)
+                    if constexpr (MASKED || BITS)
                         valid =
                             ((wh[kt] >> ((r & 3) + 8 * (r >> 2))) & 1u) != 0;
                     else if constexpr (BAND)
                         valid = key >= lo_row && key < hi_row;
                     else
                         valid = key < Sk;
-                    // BAND: -inf, a row may see no key of this tile
+                    // BAND, BITS: -inf, a row may see no key of this tile
                     st[kt][r] = valid ? st[kt][r]
-                                      : (BAND ? -__builtin_inff() : -3e30f);
+                                : (BAND || BITS ? -__builtin_inff() : -3e30f);
                 }
         }
         float mx = -3e30f;
@@ -664,7 +826,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
             for (int n = 0; n < NV; ++n)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    if constexpr (D == 128 || DH != D || BAND)
+                    if constexpr (D == 128 || DH != D || BAND || BITS)
                         o_acc[n][r] = mul_f32_scalar(o_acc[n][r], alpha);
                     else
                         o_acc[n][r] *= alpha;
@@ -720,23 +882,45 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     // (QLIST: read nlive[b][qtile] and live[b][qtile][j] for these two)
     //   word_of(t)  tile t's 64-bit mask word (MASKED) or 0 (ignored)
     // (BAND: the block's t1 - t0 and t0 + j, read before the phases above)
+    // (BITS: the list of (bm, query block), whose entries tile_no() strips of
+    // their flag and holds inside [0, n_tiles); word_of() is the block's OR
+    // word and row_word(t) this lane's own word of tile t)
     // b is uniform across the block, so are nt, every tile index and every
     // mask word: readfirstlane pins them in SGPRs, and trip counts and
-    // barriers stay block-uniform. With MASKED or BAND, nt == 0 skips the
+    // barriers stay block-uniform. With MASKED, BAND or BITS, nt == 0 skips the
     // prologue's loads, LDS writes and barrier too; the unmasked prologue is
     // unconditional, as it was before the flag existed.
     const int n_tiles = (Sk + KVBLK - 1) / KVBLK;
     // row of live/nlive: per batch element, or per (b, query block)
     const long lrow =
-        QLIST ? b * ((S + WAVES * 32 - 1) / (WAVES * 32)) + qtile : b;
-    const int* live_b = MASKED ? mask_live + lrow * n_tiles : nullptr;
+        BITS ? b * bits_bstride * ((S + WAVES * 32 - 1) / (WAVES * 32)) + qtile
+        : QLIST ? b * ((S + WAVES * 32 - 1) / (WAVES * 32)) + qtile : b;
+    const int* live_b =
+        (MASKED || BITS) ? mask_live + lrow * n_tiles : nullptr;
     const unsigned long long* words_b =
-        MASKED ? mask_words + b * n_tiles : nullptr;
+        BITS ? mask_words + lrow * n_tiles
+        : MASKED ? mask_words + b * n_tiles : nullptr;
     const int nt =
         BAND ? band_nt
+        : BITS ? min(max(__builtin_amdgcn_readfirstlane(mask_nlive[lrow]), 0),
+                     n_tiles)
         : MASKED ? __builtin_amdgcn_readfirstlane(mask_nlive[lrow]) : n_tiles;
+    // BITS: this lane's words, bits[bm][tile][row]; rows at or beyond S take
+    // the clamped row of the Q load (never stored)
+    const unsigned long long* rowp = nullptr;
+    if constexpr (BITS) {
+        const int row = q0 + l32;
+        rowp = row_bits + b * bits_bstride * n_tiles * S +
+               (row < S ? row : (S > 0 ? S - 1 : 0));
+    }
+    unsigned long long rw_cur = 0ull, rw_next = 0ull;
+    auto row_word = [&](int tile) PA_INL { return rowp[(long)tile * S]; };
+    auto tile_no = [&](int e) PA_INL {
+        if constexpr (BITS) return min(e & (PA_BITS_FULL - 1), n_tiles - 1);
+        else return e;
+    };
     auto tile_at = [&](int j) PA_INL {
-        if constexpr (MASKED)
+        if constexpr (MASKED || BITS)
             return __builtin_amdgcn_readfirstlane(live_b[j]);
         else if constexpr (BAND)
             return band_t0 + j;
@@ -744,7 +928,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
             return j;
     };
     auto word_of = [&](int tile) PA_INL -> unsigned long long {
-        if constexpr (MASKED) {
+        if constexpr (MASKED || BITS) {
             const unsigned long long w = words_b[tile];
             const unsigned int lo =
                 __builtin_amdgcn_readfirstlane((unsigned int)w);
@@ -775,29 +959,38 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
         // ONE barrier per tile; tile j+1's stores land in the other buffer
         // interleaved where the LDS port is idle (K after QK^T, V after
         // softmax); tile j+2's global loads issue before PV.
-        if ((!MASKED && !BAND) || nt > 0) {
-            const int t0 = tile_at(0);
+        if ((!MASKED && !BAND && !BITS) || nt > 0) {
+            const int t0 = tile_no(tile_at(0));
             issue_tile_loads(t0 * KVBLK, word_of(t0));
+            if constexpr (BITS) rw_cur = row_word(t0);
             write_k_lds(0);
             write_v_lds(0);
             if (nt > 1) {
-                const int t1 = tile_at(1);
+                const int t1 = tile_no(tile_at(1));
                 issue_tile_loads(t1 * KVBLK, word_of(t1));
+                if constexpr (BITS) rw_next = row_word(t1);
             }
             block_barrier();
         }
         for (int j = 0; j < nt; ++j) {
             const int p = j & 1;
-            const int tile = tile_at(j);
+            const int entry = tile_at(j);
+            const int tile = tile_no(entry);
             f32x16 st[2];
             bf16x8 pfrag[4];
             qk_phase(p, st);
             if (j + 1 < nt) write_k_lds(p ^ 1);
-            softmax_phase(tile * KVBLK, st, pfrag, word_of(tile));
+            if constexpr (BITS)
+                softmax_phase(tile * KVBLK, st, pfrag, rw_cur,
+                              (entry & PA_BITS_FULL) != 0);
+            else
+                softmax_phase(tile * KVBLK, st, pfrag, word_of(tile));
             if (j + 1 < nt) write_v_lds(p ^ 1);
+            if constexpr (BITS) rw_cur = rw_next;
             if (j + 2 < nt) {
-                const int t2 = tile_at(j + 2);
+                const int t2 = tile_no(tile_at(j + 2));
                 issue_tile_loads(t2 * KVBLK, word_of(t2));
+                if constexpr (BITS) rw_next = row_word(t2);
             }
             pv_phase(p, pfrag);
             block_barrier();
@@ -805,24 +998,32 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     } else {
         // D=64 keeps the v4 2-barrier loop (v5a measured -2.6% there —
         // halved MFMA per tile leaves too little compute to hide stores).
-        if ((!MASKED && !BAND) || nt > 0) {
-            const int t0 = tile_at(0);
+        if ((!MASKED && !BAND && !BITS) || nt > 0) {
+            const int t0 = tile_no(tile_at(0));
             issue_tile_loads(t0 * KVBLK, word_of(t0));
+            if constexpr (BITS) rw_next = row_word(t0);
         }
         for (int j = 0; j < nt; ++j) {
-            const int tile = tile_at(j);
+            const int entry = tile_at(j);
+            const int tile = tile_no(entry);
             block_barrier();
             write_k_lds(0);
             write_v_lds(0);
             block_barrier();
+            if constexpr (BITS) rw_cur = rw_next;
             if (j + 1 < nt) {
-                const int t1 = tile_at(j + 1);
+                const int t1 = tile_no(tile_at(j + 1));
                 issue_tile_loads(t1 * KVBLK, word_of(t1));
+                if constexpr (BITS) rw_next = row_word(t1);
             }
             f32x16 st[2];
             bf16x8 pfrag[4];
             qk_phase(0, st);
-            softmax_phase(tile * KVBLK, st, pfrag, word_of(tile));
+            if constexpr (BITS)
+                softmax_phase(tile * KVBLK, st, pfrag, rw_cur,
+                              (entry & PA_BITS_FULL) != 0);
+            else
+                softmax_phase(tile * KVBLK, st, pfrag, word_of(tile));
             pv_phase(0, pfrag);
         }
     }
@@ -878,11 +1079,13 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
                     // are pinned here by opaque instructions; what the
                     // compiler makes of the class kernels is pinned by the
                     // bit-equality test of the two routes.
-                    // BAND: built without packed f32, takes the same forms.
-                    if ((DH != D || BAND) && (j == 1 || j == 2))
+                    // BAND, BITS: built without packed f32, take the same
+                    // forms.
+                    constexpr bool OPAQUE = DH != D || BAND || BITS;
+                    if (OPAQUE && (j == 1 || j == 2))
                         pack[j] = EL::st(
                             mul_f32_scalar(o_acc[n][r2 * 4 + j], inv_l));
-                    else if (DH != D || BAND)
+                    else if (OPAQUE)
                         pack[j] = mul_cast_fused<E>(o_acc[n][r2 * 4 + j],
                                                     inv_l);
                     else
@@ -896,7 +1099,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     }
 }
 
-// The four BAND instantiations, built without packed fp32 VALU
+// The four BAND and four BITS instantiations, built without packed fp32 VALU
 // (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32): the target attribute of an
 // explicit instantiation applies to that instantiation alone, so every other
 // one keeps the code it had. Nothing else instantiates the flag.
@@ -912,21 +1115,25 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
 // the attribute makes that a property of the build instead of an accident
 // of the vectorizer. It may go, with PA_INL and block_barrier(), once
 // packed fp32 is accepted for new kernels; the only thing to re-check then
-// is the two bitwise tests of tests/test_gpu_attn_band.py.
-#define PA_ATTN_BAND(D_, E_)                                                  \
+// is the bitwise tests of tests/test_gpu_attn_band.py and
+// tests/test_gpu_attn_bits.py.
+#define PA_ATTN_NO_PK(D_, E_, BAND_, BITS_)                                   \
     template __global__                                                       \
     __attribute__((target("no-packed-fp32-ops"))) void                        \
-    attn_fwd_v4_kernel<D_, E_, false, false, false, D_, true>(                \
+    attn_fwd_v4_kernel<D_, E_, false, false, false, D_, BAND_, BITS_>(        \
         const E_*, const E_*, const E_*, E_*, int, int, float, int, long,     \
         long, int, long, long, int, long, long, int, long, long, int, int,    \
         E_*, int, long, long, int, const unsigned long long*, const int*,     \
         const int*, float*, long, long, long, const int*, const int*,         \
-        const int*);
-PA_ATTN_BAND(64, bf16)
-PA_ATTN_BAND(64, _Float16)
-PA_ATTN_BAND(128, bf16)
-PA_ATTN_BAND(128, _Float16)
-#undef PA_ATTN_BAND
+        const int*, const unsigned long long*, int);
+#define PA_ATTN_BAND_BITS(D_, E_)                                             \
+    PA_ATTN_NO_PK(D_, E_, true, false) PA_ATTN_NO_PK(D_, E_, false, true)
+PA_ATTN_BAND_BITS(64, bf16)
+PA_ATTN_BAND_BITS(64, _Float16)
+PA_ATTN_BAND_BITS(128, bf16)
+PA_ATTN_BAND_BITS(128, _Float16)
+#undef PA_ATTN_BAND_BITS
+#undef PA_ATTN_NO_PK
 
 // Packed key mask as the MASKED kernels take it (see pack_key_mask). With a
 // block mask, live is [B, nq, nk] and nlive [B, nq] (see pack_block_lists),
@@ -938,6 +1145,11 @@ struct AttnKeyMask {
 // Packed row bounds as the BAND kernels take them (see pack_row_bounds).
 struct AttnBand {
     at::Tensor lo_c, hi_c, range;
+};
+
+// A packed dense mask as the BITS kernels take it (see pack_attn_mask).
+struct AttnBits {
+    at::Tensor bits, words, list, nlist;
 };
 
 // Arguments of one attention launch, in the kernel's parameter order.
@@ -965,6 +1177,8 @@ struct AttnArgs {
     float* lse;
     long l_bs, l_hs, l_ss;
     const int *band_lo, *band_hi, *band_range;
+    const unsigned long long* row_bits;
+    int bits_bstride;
 };
 
 // Head dims the attention kernels serve as they are, as X(head dim, tile
@@ -992,19 +1206,19 @@ std::vector<long> attn_native_head_dims() {
 }
 
 template <int D, bool MASKED, bool QLIST, bool LSE, int DH,
-          bool BAND = false>
+          bool BAND = false, bool BITS = false>
 static void launch_attn_v4_as(at::ScalarType st, dim3 grid,
                               const AttnArgs& a) {
     PA_WITH_ELEM16(st, hipLaunchKernelGGL(
         HIP_KERNEL_NAME(
-            attn_fwd_v4_kernel<D, E, MASKED, QLIST, LSE, DH, BAND>),
+            attn_fwd_v4_kernel<D, E, MASKED, QLIST, LSE, DH, BAND, BITS>),
         grid, dim3(512), 0,
         cur_stream(), (const E*)a.q, (const E*)a.k, (const E*)a.v, (E*)a.out,
         a.S, a.Sk, a.scale, a.H, a.q_bs, a.q_hs, a.q_ss, a.k_bs, a.k_hs,
         a.k_ss, a.v_bs, a.v_hs, a.v_ss, a.o_bs, a.o_hs, a.o_ss, a.xcd_grid,
         (E*)a.out2, a.s_split, a.o2_bs, a.o2_hs, a.o2_ss, a.mask_words,
         a.mask_live, a.mask_nlive, a.lse, a.l_bs, a.l_hs, a.l_ss, a.band_lo,
-        a.band_hi, a.band_range));
+        a.band_hi, a.band_range, a.row_bits, a.bits_bstride));
 }
 
 // The table's instantiation for head dim D. The caller has checked that the
@@ -1029,10 +1243,13 @@ static void launch_attn_v4(int D, at::ScalarType st, dim3 grid,
 // the fp32 log-sum-exp, in the output's layout without D, to the result; it
 // goes with neither a split nor a block mask. band != nullptr selects the
 // BAND instantiations: head dims 64 and 128, and nothing of the above.
+// bits != nullptr selects the BITS instantiations: head dims 64 and 128,
+// with or without a split, and nothing else of the above.
 static std::vector<at::Tensor> attn_fwd_launch(
     at::Tensor q, at::Tensor k, at::Tensor v, double scale, bool bshd,
     bool has_split, long split, const AttnKeyMask* km,
-    bool want_lse = false, const AttnBand* band = nullptr) {
+    bool want_lse = false, const AttnBand* band = nullptr,
+    const AttnBits* bits = nullptr) {
     CHECK_GPU(q);
     TORCH_CHECK(is_elem16(q.scalar_type()),
                 "attn_fwd: bf16 or fp16 only, got ", q.scalar_type());
@@ -1077,6 +1294,10 @@ static std::vector<at::Tensor> attn_fwd_launch(
                                     km == nullptr),
                 "attn_fwd: row bounds run at head dims 64 and 128, without "
                 "a key or block mask, split or log-sum-exp");
+    TORCH_CHECK(bits == nullptr || (D == cls && !want_lse && km == nullptr &&
+                                    band == nullptr),
+                "attn_fwd: dense masks run at head dims 64 and 128, without "
+                "a key or block mask, row bounds or log-sum-exp");
     TORCH_CHECK(!has_split || (split > 0 && split < S),
                 "attn_fwd: split must lie inside (0, S = ", S, "), got ",
                 split);
@@ -1167,6 +1388,36 @@ static std::vector<at::Tensor> attn_fwd_launch(
                         band->range.is_contiguous(),
                     "attn_fwd: row bounds tensors must be contiguous");
     }
+    if (bits != nullptr) {
+        // what the kernel indexes: bits by (bm, tile, query row), words and
+        // list by (bm, query block, tile), nlist by (bm, query block); the
+        // list's contents only through a clamp to the tile count
+        const long nqb = (S + 255) / 256, n_tiles = (Sk + 63) / 64;
+        const at::Tensor* ts[4] = {&bits->bits, &bits->words, &bits->list,
+                                   &bits->nlist};
+        for (const at::Tensor* t : ts)
+            TORCH_CHECK(t->device() == qc.device() && t->is_contiguous(),
+                        "attn_fwd: dense mask tensors must be contiguous and "
+                        "on q's device");
+        TORCH_CHECK(bits->bits.scalar_type() == at::kLong &&
+                        bits->words.scalar_type() == at::kLong &&
+                        bits->list.scalar_type() == at::kInt &&
+                        bits->nlist.scalar_type() == at::kInt,
+                    "attn_fwd: dense mask needs int64 bits and words, int32 "
+                    "list and nlist");
+        const long Bm = bits->bits.dim() == 3 ? bits->bits.size(0) : -1;
+        TORCH_CHECK(Bm == 1 || Bm == B,
+                    "attn_fwd: dense mask batch must be 1 or q's batch (", B,
+                    ")");
+        const bool fits =
+            bits->bits.size(1) == n_tiles && bits->bits.size(2) == S &&
+            bits->words.sizes() == at::IntArrayRef({Bm, nqb, n_tiles}) &&
+            bits->list.sizes() == at::IntArrayRef({Bm, nqb, n_tiles}) &&
+            bits->nlist.sizes() == at::IntArrayRef({Bm, nqb});
+        TORCH_CHECK(fits, "attn_fwd: dense mask was packed for another "
+                    "(Sq, Sk) than (", S, ", ", Sk, "): bits ",
+                    bits->bits.sizes(), ", list ", bits->list.sizes());
+    }
     const bool do_split = has_split && bshd;
     at::Tensor out = bshd
         ? at::empty({B, do_split ? (int)split : S, H, D}, qc.options())
@@ -1208,16 +1459,31 @@ static std::vector<at::Tensor> attn_fwd_launch(
         do_split ? out2.data_ptr() : nullptr, do_split ? (int)split : S,
         do_split ? out2.stride(0) : 0, do_split ? out2.stride(2) : 0,
         do_split ? (int)out2.stride(1) : 0,
-        km ? (const unsigned long long*)km->words.data_ptr() : nullptr,
-        km ? km->live.data_ptr<int>() : nullptr,
-        km ? km->nlive.data_ptr<int>() : nullptr,
+        km     ? (const unsigned long long*)km->words.data_ptr()
+        : bits ? (const unsigned long long*)bits->words.data_ptr() : nullptr,
+        km     ? km->live.data_ptr<int>()
+        : bits ? bits->list.data_ptr<int>() : nullptr,
+        km     ? km->nlive.data_ptr<int>()
+        : bits ? bits->nlist.data_ptr<int>() : nullptr,
         want_lse ? lse.data_ptr<float>() : nullptr,
         want_lse ? lse.stride(b_ax) : 0, want_lse ? lse.stride(h_ax) : 0,
         want_lse ? lse.stride(s_ax) : 0,
         band ? band->lo_c.data_ptr<int>() : nullptr,
         band ? band->hi_c.data_ptr<int>() : nullptr,
-        band ? band->range.data_ptr<int>() : nullptr};
+        band ? band->range.data_ptr<int>() : nullptr,
+        bits ? (const unsigned long long*)bits->bits.data_ptr() : nullptr,
+        bits && bits->bits.size(0) == B ? 1 : 0};
     const at::ScalarType st = qc.scalar_type();
+    if (bits != nullptr) {
+        if (D == 64)
+            launch_attn_v4_as<64, false, false, false, 64, false, true>(
+                st, grid, a);
+        else
+            launch_attn_v4_as<128, false, false, false, 128, false, true>(
+                st, grid, a);
+        if (do_split) return {out, out2};
+        return {out};
+    }
     if (band != nullptr) {
         if (D == 64)
             launch_attn_v4_as<64, false, false, false, 64, true>(st, grid, a);
@@ -1324,4 +1590,28 @@ at::Tensor attn_fwd_bshd_band(at::Tensor q, at::Tensor k, at::Tensor v,
     const AttnBand band{lo_c, hi_c, range};
     return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, false, 0, nullptr,
                            /*want_lse=*/false, &band)[0];
+}
+
+at::Tensor attn_fwd_bits(at::Tensor q, at::Tensor k, at::Tensor v,
+                         double scale, at::Tensor bits, at::Tensor words,
+                         at::Tensor list, at::Tensor nlist) {
+    const AttnBits ab{bits, words, list, nlist};
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/false, false, 0, nullptr,
+                           /*want_lse=*/false, nullptr, &ab)[0];
+}
+
+at::Tensor attn_fwd_bshd_bits(at::Tensor q, at::Tensor k, at::Tensor v,
+                              double scale, at::Tensor bits, at::Tensor words,
+                              at::Tensor list, at::Tensor nlist) {
+    const AttnBits ab{bits, words, list, nlist};
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, false, 0, nullptr,
+                           /*want_lse=*/false, nullptr, &ab)[0];
+}
+
+std::vector<at::Tensor> attn_fwd_bshd_split_bits(
+    at::Tensor q, at::Tensor k, at::Tensor v, double scale, long split,
+    at::Tensor bits, at::Tensor words, at::Tensor list, at::Tensor nlist) {
+    const AttnBits ab{bits, words, list, nlist};
+    return attn_fwd_launch(q, k, v, scale, /*bshd=*/true, true, split,
+                           nullptr, /*want_lse=*/false, nullptr, &ab);
 }

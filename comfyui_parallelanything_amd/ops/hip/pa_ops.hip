@@ -76,6 +76,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "attn_fwd with packed row bounds: row i sees keys [lo[i], hi[i])");
     m.def("attn_fwd_bshd_band", &attn_fwd_bshd_band,
           "attn_fwd_bshd with packed row bounds");
+    m.def("pack_attn_mask", &pack_attn_mask,
+          "[Bm,Sq,Sk] bool mask -> {bits [Bm,nk,Sq] int64, words [Bm,nq,nk] "
+          "int64, list [Bm,nq,nk] int32, nlist [Bm,nq] int32}");
+    m.def("attn_fwd_bits", &attn_fwd_bits,
+          "attn_fwd with a packed dense mask: one 64-bit word per row and tile");
+    m.def("attn_fwd_bshd_bits", &attn_fwd_bshd_bits,
+          "attn_fwd_bshd with a packed dense mask");
+    m.def("attn_fwd_bshd_split_bits", &attn_fwd_bshd_split_bits,
+          "attn_fwd_bshd_split with a packed dense mask");
     m.def("attn_fwd_masked", &attn_fwd_masked,
           "attn_fwd with a packed key-padding mask (dead tiles skipped)");
     m.def("attn_fwd_bshd_masked", &attn_fwd_bshd_masked,

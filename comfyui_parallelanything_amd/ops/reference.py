@@ -286,6 +286,37 @@ NO_ROW_BOUNDS_WITH_MASK = ("row_bounds= together with key_mask= or "
                            "block_mask= is not supported")
 
 
+def as_bool_attn_mask(mask: torch.Tensor, B: int, Sq: int,
+                      Sk: int) -> torch.Tensor:
+    """Dense bool/integer attention mask (nonzero = attend), [Sq, Sk], [Bm,
+    Sq, Sk] or [Bm, 1, Sq, Sk] with Bm in {1, B}, shared by heads -> bool
+    [Bm, Sq, Sk]. Floating masks are refused for as_bool_key_mask's reason;
+    a head dimension other than 1 and any other shape raise ValueError."""
+    if mask.dtype.is_floating_point or mask.dtype.is_complex:
+        raise ValueError(
+            f"attn_mask must be bool or integer (nonzero = attend), got "
+            f"{mask.dtype}: additive float biases are not supported")
+    shape = tuple(mask.shape)
+    if mask.dim() == 4 and shape[1] != 1:
+        raise ValueError(
+            f"attn_mask is shared by heads: its head dimension must be 1, "
+            f"got {list(shape)} (per-head masks are not supported)")
+    if mask.dim() == 4:
+        mask = mask[:, 0]
+    elif mask.dim() == 2:
+        mask = mask[None]
+    if (mask.dim() != 3 or tuple(mask.shape[1:]) != (Sq, Sk)
+            or mask.shape[0] not in (1, B)):
+        raise ValueError(
+            f"attn_mask must be [Sq, Sk], [Bm, Sq, Sk] or [Bm, 1, Sq, Sk] "
+            f"with Sq={Sq}, Sk={Sk} and Bm 1 or {B}, got {list(shape)}")
+    return mask if mask.dtype == torch.bool else mask != 0
+
+
+NO_ATTN_MASK_WITH_MASK = ("attn_mask= together with key_mask=, block_mask= "
+                          "or row_bounds= is not supported")
+
+
 def check_qkv(q, k, v, bshd: bool = False, split: Optional[int] = None):
     """k and v must have q's batch, head count and head dim, and one length
     between them; ``split`` lies inside (0, Sq). The native kernel indexes k
@@ -317,6 +348,7 @@ def attention(
     block_mask: Optional[torch.Tensor] = None,
     return_lse: bool = False,
     row_bounds=None,
+    attn_mask: Optional[torch.Tensor] = None,
 ):
     """Plain attention, [B, H, S, D] -> [B, H, S, D]. fp32 softmax.
 
@@ -345,10 +377,24 @@ def attention(
     key_mask= or block_mask= (ValueError). K/V inside [0, Sk) must be
     finite (see ops.pack_row_bounds).
 
+    attn_mask: optional dense bool/integer mask, [Sq, Sk], [Bm, Sq, Sk] or
+    [Bm, 1, Sq, Sk] with Bm in {1, B}, shared by heads. Key j is visible to
+    query row i of batch element b iff attn_mask[b or 0][i][j] != 0. A row
+    with no visible key gives zeros; K/V rows no query row of the batch
+    element sees are don't-care (zeroed before the matmuls). Not supported
+    together with any other mask, or with return_lse (ValueError).
+
     k and v have q's batch, head count and head dim (ValueError otherwise:
     nothing is broadcast, as on the native kernels). Sk = 0 gives zeros.
     """
     check_qkv(q, k, v)
+    if attn_mask is not None:
+        if not (key_mask is None and block_mask is None
+                and row_bounds is None):
+            raise ValueError(f"attention: {NO_ATTN_MASK_WITH_MASK}")
+        if return_lse:
+            raise ValueError("attention: attn_mask= is not supported "
+                             "together with the log-sum-exp output")
     if row_bounds is not None and not (key_mask is None
                                        and block_mask is None):
         raise ValueError(f"attention: {NO_ROW_BOUNDS_WITH_MASK}")
@@ -375,6 +421,9 @@ def attention(
                   for t in as_row_bounds(row_bounds, Sq, Sk))
         j = torch.arange(Sk, device=q.device)[None, :]
         vis = ((j >= lo) & (j < hi))[None, None]        # [1, 1, Sq, Sk]
+    if attn_mask is not None:
+        vis = as_bool_attn_mask(attn_mask, B, Sq, Sk).to(
+            q.device)[:, None]                          # [Bm, 1, Sq, Sk]
     qf, kf, vf = _wide(q), _wide(k), _wide(v)
     if vis is not None:
         # Unmasked calls skip this: a copy of k or v can take matmul down

@@ -29,6 +29,15 @@ frame_span_row_bounds over --frames (B may be `all`), packed once outside
 the timed loop. Printed beside each time: the fraction of (query block,
 tile) pairs the kernel visits, which times the dense time is the yardstick.
 
+--attn-mask {full,causal,regions} runs the dense-mask kernels instead (no
+other mask, no --lse): full = every key visible (against the unmasked call
+and --key-mask full), causal = the dense form of ops.causal_row_bounds
+(against --row-bounds causal), regions = layers.regional_joint_mask over 512
+text tokens in two spans and a 64-wide image grid split left / right (needs
+Sq = Sk = 512 + 64 h). The [Sq, Sk] mask is packed once outside the timed
+loop; the pack is timed on its own and printed with the fraction of (query
+block, tile) pairs the kernel visits.
+
 The sd15_* rows are SD1.5's head dims (8 heads over 320 / 640 channels, and
 the 77-token cross-attention). They run as the UNet calls them: ops.
 attention_bshd on [B, S, H, D] tensors, then .flatten(2). --only NAMES keeps
@@ -112,6 +121,8 @@ def main():
     ap.add_argument("--block-mask", default="none", metavar="none|full|frame:W")
     ap.add_argument("--row-bounds", default="none",
                     metavar="none|causal|frame:B,A")
+    ap.add_argument("--attn-mask", default="none",
+                    choices=("none", "full", "causal", "regions"))
     ap.add_argument("--frames", type=int, default=0,
                     help="run the WAN 720p shape with this many latent "
                          "frames (3600 tokens each) instead of the table")
@@ -147,6 +158,10 @@ def main():
     if args.row_bounds != "none" and (
             args.lse or args.key_mask != "none" or args.block_mask != "none"):
         ap.error("--row-bounds takes no --lse, key mask or block mask")
+    if args.attn_mask != "none" and (
+            args.lse or args.key_mask != "none" or args.block_mask != "none"
+            or args.row_bounds != "none"):
+        ap.error("--attn-mask takes no --lse and no other mask")
     dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
     assert torch.cuda.is_available()
     dev = "cuda"
@@ -157,7 +172,7 @@ def main():
     attn = ops.attention_lse if args.lse else ops.attention
     print(f"== attention{' + lse' if args.lse else ''} ({args.dtype}, random data, "
           f"key mask: {args.key_mask}, block mask: {args.block_mask}, "
-          f"row bounds: {args.row_bounds}) ==")
+          f"row bounds: {args.row_bounds}, attn mask: {args.attn_mask}) ==")
     tokens_per_frame = 3600  # 720p: (720/16) x (1280/16) latent patches
     video = {f"wan720p_f{args.frames}": (
         1, 40, args.frames * tokens_per_frame,
@@ -184,9 +199,9 @@ def main():
     for name, (B, H, S, Sk, D) in table.items():
         bshd = name.startswith("sd15_")
         if bshd and (args.lse or args.block_mask != "none"
-                     or args.row_bounds != "none"):
+                     or args.row_bounds != "none" or args.attn_mask != "none"):
             ap.error(f"{name} runs attention_bshd: no --lse, no block mask, "
-                     f"no row bounds")
+                     f"no row bounds, no dense mask")
         q = torch.randn(B, H, S, D, device=dev, dtype=dtype)
         k = torch.randn(B, H, Sk, D, device=dev, dtype=dtype)
         v = torch.randn_like(k)
@@ -215,6 +230,26 @@ def main():
             rng = rb.range.cpu()
             visited = (rng[:, 1] - rng[:, 0]).sum().item()
             note = f"  visited {visited / (rng.shape[0] * ((Sk + 63) // 64)):.4f}"
+        if args.attn_mask != "none":
+            if args.attn_mask == "full":
+                dense = torch.ones(S, Sk, dtype=torch.bool, device=dev)
+            elif args.attn_mask == "causal":
+                hi = ops.causal_row_bounds(S, Sk, device=dev)[1]
+                dense = torch.arange(Sk, device=dev)[None, :] < hi[:, None]
+            else:
+                from comfyui_parallelanything_amd.models import layers
+                rows = (S - 512) // 64
+                if S != Sk or rows < 1 or 512 + 64 * rows != S:
+                    ap.error("--attn-mask regions needs Sq = Sk = 512 + 64 h")
+                left = torch.zeros(rows, 64, dtype=torch.bool, device=dev)
+                left[:, :32] = True
+                dense = layers.regional_joint_mask(
+                    512, rows, 64, [(0, 256, left), (256, 512, ~left)])
+            am = ops.pack_attn_mask(dense, B, S, Sk)
+            pack = timeit(lambda: ops.pack_attn_mask(dense, B, S, Sk))
+            mk = {"attn_mask": am}
+            visited = am.nlist.sum().item() / am.list[0].numel()
+            note = f"  visited {visited:.4f}  pack {pack*1e3:.3f} ms"
         if bshd:
             dt = timeit(lambda: ops.attention_bshd(q, k, v, **mk).flatten(2),
                         iters=200, warmup=20)
