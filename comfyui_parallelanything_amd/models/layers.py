@@ -134,12 +134,24 @@ class MLPEmbedder(nn.Module):
     def forward_timestep(self, t: torch.Tensor,
                          max_period: float = 10000.0,
                          time_factor: float = 1000.0) -> torch.Tensor:
-        """Timestep scalar [B] -> conditioning vector [B, hidden].
+        """Timestep scalar [B] -> conditioning vector [B, hidden]; [B, f],
+        one timestep per latent frame, -> [B, f, hidden]. Each frame column
+        takes the [B] path on its own, so its rows are bit for bit the [B]
+        call's at those timesteps (the rounding of a GEMM depends on its
+        row count, flattened to [B * f] they would differ in the last
+        place). Any other shape raises ValueError.
 
         GPU: fused sinusoid+in_layer+SiLU kernel (SURVEY §2b timestep-MLP
         fusion; one launch instead of three and the sinusoid stays fp32
         into the accumulate), then the out_layer GEMM. CPU / non-bf16:
         composed ops."""
+        if t.dim() == 2:
+            return torch.stack(
+                [self.forward_timestep(col, max_period, time_factor)
+                 for col in t.unbind(1)], dim=1)
+        if t.dim() != 1:
+            raise ValueError(f"timesteps must be [B] or [B, f] (one per "
+                             f"latent frame), got {list(t.shape)}")
         # in_layer may be FP8Linear-swapped (no .weight attr): compose then
         w = getattr(self.in_layer, "weight", None)
         if (w is not None and t.is_cuda and w.dtype == torch.bfloat16

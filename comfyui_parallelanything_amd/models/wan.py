@@ -57,7 +57,10 @@ class WanBlock(nn.Module):
 
     def forward(self, x, e, context, pe, key_mask=None, block_mask=None,
                 self_attn=None, row_bounds=None):
-        # e: [B, 6, dim] time-modulation; learned bias added per block
+        # e: [B, 6, dim] time-modulation, or [B, f, 6, dim] with a timestep
+        # per latent frame; learned bias added per block. The six views go
+        # to the ops as they are: [B, dim], or [B, f, dim] rows of the
+        # grouped modulation kernels
         # key_mask: optional ops.KeyMask over the context tokens — masks the
         # cross-attention only
         # block_mask: optional ops.BlockMask over the space-time tokens —
@@ -67,7 +70,7 @@ class WanBlock(nn.Module):
         # self_attn: optional (q, k, v, scale) -> [B,S,H,D] in place of the
         # local self-attention: x is a token shard and the keys live on other
         # ranks (parallel.sequence)
-        m = (e + self.mod).unbind(dim=1)  # 6 x [B, dim]
+        m = (e + self.mod).unbind(dim=-2)  # 6 x [B, dim] or [B, f, dim]
         shift1, scale1, gate1, shift2, scale2, gate2 = m
 
         qkv = ln_mod_into(self.self_qkv, x, scale1, shift1).unflatten(
@@ -232,6 +235,29 @@ class WanDiT(nn.Module):
             self._mask_cache[key] = rb
         return rb
 
+    def _per_frame_timesteps(self, timesteps, B, f) -> bool:
+        """False for timesteps [B], True for [B, f] (one per latent frame
+        after patchify: image-to-video's clean first frame, diffusion
+        forcing); ValueError for any other shape, and for [B, f] where it
+        cannot be served."""
+        if tuple(timesteps.shape) == (B,):
+            return False
+        if tuple(timesteps.shape) != (B, f):
+            raise ValueError(
+                f"timesteps must be [B] = [{B}] or [B, f] = [{B}, {f}] (one "
+                f"per latent frame), got {list(timesteps.shape)}")
+        if self._seq_parallel is not None:
+            raise ValueError(
+                "per-frame timesteps [B, f] with sequence parallelism are "
+                "not supported: a token shard need not start on a frame "
+                "edge, so its rows do not split into whole frames")
+        if any(hasattr(m, "ln_quant") for m in self.modules()):
+            raise ValueError(
+                "per-frame timesteps [B, f] with the fp8 serving mode are "
+                "not supported: layer_norm_mod_fp8 takes [B, D] modulation "
+                "only")
+        return True
+
     def _pe(self, f, h, w, device):
         key = (f, h, w, str(device))
         pe = self._pe_cache.get(key)
@@ -259,6 +285,7 @@ class WanDiT(nn.Module):
         B, C, F, H, W = x.shape
         pf, ph, pw = cfg.patch_size
         f, h, w = F // pf, H // ph, W // pw
+        per_frame = self._per_frame_timesteps(timesteps, B, f)
         if cfg.cond_channels:
             # I2V: concatenate mask + reference-image latent channels
             # (batch-shaped kwarg, so the engine's kwargs-split rules
@@ -291,7 +318,16 @@ class WanDiT(nn.Module):
             context = torch.zeros(B, 1, cfg.ctx_dim, device=x.device, dtype=x.dtype)
         ctx = self.txt_in(context)
         tvec = self.time_in.forward_timestep(timesteps)
-        e = self.time_proj(torch.nn.functional.silu(tvec)).view(B, 6, cfg.dim)
+        if per_frame:
+            # [B, f, dim]: the two projections take a frame column at a
+            # time, as forward_timestep does and for its reason, so a frame
+            # at timestep t is modulated bit for bit as the [B] forward at t
+            silu_t = torch.nn.functional.silu(tvec).unbind(1)
+            e = torch.stack([self.time_proj(s) for s in silu_t],
+                            dim=1).view(B, f, 6, cfg.dim)
+            head_mod = torch.stack([self.head_mod(s) for s in silu_t], dim=1)
+        else:
+            e = self.time_proj(torch.nn.functional.silu(tvec)).view(B, 6, cfg.dim)
         mk = {}
         if attention_mask is not None:
             # packed once per forward, shared by every block's cross-attention
@@ -306,7 +342,9 @@ class WanDiT(nn.Module):
             mk["self_attn"] = sp.attention
         for block in self.transformer_blocks:
             seq = block(seq, e, ctx, pe, **mk)
-        shift, scale = self.head_mod(torch.nn.functional.silu(tvec)).chunk(2, dim=-1)
+        if not per_frame:
+            head_mod = self.head_mod(torch.nn.functional.silu(tvec))
+        shift, scale = head_mod.chunk(2, dim=-1)
         out = self.head(ops.layer_norm_mod(seq, scale, shift))
         if sp is not None:
             out = sp.gather(out)    # every rank holds every token's output

@@ -175,8 +175,53 @@ def rms_norm(x: torch.Tensor, weight=None, eps: float = 1e-6) -> torch.Tensor:
     return reference.rms_norm(x, weight, eps)
 
 
+# Limit of the grouped modulation kernels (ops/hip/mod_groups.h): 16 granules
+# of 16 bytes a lane
+_MOD_GROUPS_MAX_D = 8192
+
+
+def _mod_groups_native(op: str, x):
+    """The extension when the grouped kernels cover x, else None after the
+    one-time note (or without one where there is no extension to ask)."""
+    ext = _require_ext(op + "_grouped")
+    if ext is None:
+        return None
+    D = x.shape[-1]
+    if x.dtype in _NATIVE16 and D % 8 == 0 and D <= _MOD_GROUPS_MAX_D:
+        return ext
+    _unsupported(op, f"grouped modulation, dtype={x.dtype}, D={D}")
+    return None
+
+
 def layer_norm_mod(x, scale, shift, eps: float = 1e-6) -> torch.Tensor:
+    """LN(x) * (1 + scale) + shift over the last dim of x [B, S, D], no
+    learned affine. scale and shift are [B, D], one row per batch element,
+    or the grouped [B, G, D] with G >= 1 dividing S: row s of batch element
+    b takes modulation row [b][s // (S // G)]. G = frames is a timestep per
+    latent frame, G = S per-token modulation, G = 1 the [B, D] case in 3-D
+    form.
+
+    Grouped calls on the GPU run layer_norm_mod_grouped_kernel for bf16 and
+    fp16 with D % 8 == 0 and D <= 8192; anything else there takes the
+    reference path with the one-time warning. The modulation is read as it
+    is, at any batch and group-row stride (the unbind(-2) views of a [B, G,
+    6, D] projection), and copied only when its last dim is not contiguous
+    or a row does not start on 16 bytes. Nothing is read on the host.
+    Refused on every device: S % G != 0 (ValueError); another B or D, a
+    dtype or device other than x's, scale and shift of different shapes
+    (RuntimeError). Zero-element inputs return the empty result."""
+    grouped = x.dim() == 3 and scale.dim() == 3 and shift.dim() == 3
+    if grouped:
+        reference.check_mod_groups("layer_norm_mod", x, scale=scale,
+                                   shift=shift)
+        if x.numel() == 0:
+            return torch.empty_like(x)
     if x.is_cuda:
+        if grouped:
+            ext = _mod_groups_native("layer_norm_mod", x)
+            if ext is not None:
+                return ext.layer_norm_mod_grouped(x, scale, shift, eps)
+            return reference.layer_norm_mod(x, scale, shift, eps)
         ext = _require_ext("layer_norm_mod")
         if ext is not None:
             if scale.dim() == x.dim() - 1:
@@ -191,7 +236,26 @@ def layer_norm_mod(x, scale, shift, eps: float = 1e-6) -> torch.Tensor:
 def gate_residual(residual, gate, x) -> torch.Tensor:
     """residual + gate * x; x and residual [B, S, D], gate [B, D] (one row
     per batch element: a broadcast [1, D] gate, another D, or a residual of
-    another shape raises). Zero-element inputs give an empty result."""
+    another shape raises) or the grouped [B, G, D] of layer_norm_mod, with
+    its coverage, layout rule and refusals (gate_residual_grouped_kernel).
+    Zero-element inputs give an empty result."""
+    grouped = x.dim() == 3 and gate.dim() == 3
+    if grouped:
+        reference.check_mod_groups("gate_residual", x, gate=gate)
+        _refuse_unless(
+            residual.shape == x.shape,
+            f"gate_residual: residual {list(residual.shape)} must have x's "
+            f"shape {list(x.shape)}")
+        _refuse_unless(
+            residual.dtype == x.dtype and residual.device == x.device,
+            "gate_residual: residual dtype and device must match x's")
+        if x.numel() == 0:
+            return torch.empty_like(x)
+        if x.is_cuda:
+            ext = _mod_groups_native("gate_residual", x)
+            if ext is not None:
+                return ext.gate_residual_grouped(residual, gate, x)
+        return reference.gate_residual(residual, gate, x)
     if x.dim() == 3 and gate.dim() == 2 and not x.is_cuda:
         _refuse_unless(
             tuple(gate.shape) == (x.shape[0], x.shape[2]),

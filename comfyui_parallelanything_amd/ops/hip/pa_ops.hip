@@ -22,6 +22,7 @@
 #include "common.h"
 #include "norm.h"
 #include "token_ops.h"
+#include "mod_groups.h"
 #include "group_norm_nhwc.h"
 #include "elementwise.h"
 #include "qk_pack.h"
@@ -43,6 +44,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("geglu", &geglu,
           "GEGLU a * erf-gelu(g) of [rows, 2N] row-strided halves (gfx950)");
     m.def("gate_residual", &gate_residual, "Gated residual add (gfx950)");
+    m.def("layer_norm_mod_grouped", &layer_norm_mod_grouped,
+          "AdaLN LayerNorm with [B, G, D] modulation: row s takes modulation "
+          "row s / (S / G) (gfx950)");
+    m.def("gate_residual_grouped", &gate_residual_grouped,
+          "Gated residual add with a [B, G, D] gate (gfx950)");
     m.def("group_norm_silu", &group_norm_silu, "GroupNorm+SiLU (gfx950)",
           py::arg("x"), py::arg("groups"), py::arg("weight") = py::none(),
           py::arg("bias") = py::none(), py::arg("eps") = 1e-6);

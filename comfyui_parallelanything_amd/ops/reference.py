@@ -32,28 +32,61 @@ def rms_norm(x: torch.Tensor, weight: Optional[torch.Tensor], eps: float = 1e-6)
     return out.to(dtype)
 
 
+def mod_rows(mod: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """A modulation operand broadcastable against x [B, S, D]: [B, D] gets
+    its sequence axis; [B, G, D] with 1 < G < S is the grouped form, row s
+    taking modulation row s // (S // G); G = 1 and G = S go as they are."""
+    if mod.dim() == x.dim() - 1:
+        return mod.unsqueeze(1)
+    if mod.dim() == 3 and x.dim() == 3 and mod.shape[1] not in (1, x.shape[1]):
+        return mod.repeat_interleave(x.shape[1] // mod.shape[1], dim=1)
+    return mod
+
+
+def check_mod_groups(op: str, x: torch.Tensor, **mods: torch.Tensor) -> None:
+    """The refusals of the grouped form, x [B, S, D] beside [B, G, D]
+    modulation: S % G != 0 raises ValueError; another B or D, another dtype
+    or device than x's, or operands of different shapes RuntimeError, as the
+    [B, D] form does."""
+    B, S, D = x.shape
+    first = None
+    for name, m in mods.items():
+        G = m.shape[1]
+        if (m.shape[0], m.shape[2]) != (B, D):
+            raise RuntimeError(f"{op}: {name} must be [B, G, D] = [{B}, G, "
+                               f"{D}], got {list(m.shape)}")
+        if G < 1 or S % G != 0:
+            raise ValueError(f"{op}: S = {S} is not a multiple of G = {G} "
+                             f"({name} {list(m.shape)})")
+        if m.dtype != x.dtype or m.device != x.device:
+            raise RuntimeError(f"{op}: {name} is {m.dtype} on {m.device}, x "
+                               f"{x.dtype} on {x.device}")
+        if first is not None and m.shape != first[1].shape:
+            raise RuntimeError(f"{op}: {first[0]} {list(first[1].shape)} and "
+                               f"{name} {list(m.shape)} must have one shape")
+        first = first or (name, m)
+
+
 def layer_norm_mod(
     x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, eps: float = 1e-6
 ) -> torch.Tensor:
     """AdaLN-modulated LayerNorm: LN(x) * (1 + scale) + shift.
 
-    x: [B, S, D]; scale/shift: [B, D] (broadcast over S) or [B, S, D].
+    x: [B, S, D]; scale/shift: [B, D] (broadcast over S), [B, S, D], or the
+    grouped [B, G, D] with S % G == 0 (mod_rows).
     No learned affine — modulation plays that role (MMDiT convention).
     """
     dtype = x.dtype
     out = F.layer_norm(_wide(x), (x.shape[-1],), eps=eps)
-    if scale.dim() == x.dim() - 1:
-        scale = scale.unsqueeze(1)
-        shift = shift.unsqueeze(1)
+    scale, shift = mod_rows(scale, x), mod_rows(shift, x)
     out = out * (1.0 + _wide(scale)) + _wide(shift)
     return out.to(dtype)
 
 
 def gate_residual(residual: torch.Tensor, gate: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
-    """residual + gate * x with gate [B, D] broadcast over sequence."""
-    if gate.dim() == x.dim() - 1:
-        gate = gate.unsqueeze(1)
-    return residual + gate * x
+    """residual + gate * x with gate [B, D] broadcast over sequence, or the
+    grouped [B, G, D] (mod_rows)."""
+    return residual + mod_rows(gate, x) * x
 
 
 def group_norm_silu(

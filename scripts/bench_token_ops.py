@@ -11,6 +11,16 @@ cache, and reported as ms per call and effective GB/s for the bytes one
 pass has to move, against the ~6300 GB/s roofline.
 
     python scripts/bench_token_ops.py --rounds 3
+
+--grouped times the grouped modulation kernels instead (docs/KERNELS.md,
+"Grouped modulation"): ops.layer_norm_mod and ops.gate_residual on x [1, S,
+D] with [1, G, D] modulation, bf16, three kinds of run alternating per round:
+(a) the composed reference path on the device with the modulation expanded
+to [1, S, D] (expanded once, outside the timing), which was the only route
+for such a call before the kernels; (b) the [B, D] kernels on the same x,
+which move the same bytes; (c) the grouped kernels.
+
+    python scripts/bench_token_ops.py --grouped --rounds 3
 """
 from __future__ import annotations
 
@@ -73,6 +83,57 @@ def sides(op: str, width: int, dtype, g):
     return eager, lambda xd: ops.layer_norm(xd[1], w, b, residual=xd[0])
 
 
+GROUPED_SHAPES = ((75600, 21, 5120), (75600, 21, 3072))    # WAN 14B, 5B
+
+
+def grouped(args):
+    """(a) reference, (b) [B, D] kernels, (c) grouped kernels, alternating."""
+    from comfyui_parallelanything_amd.ops import reference
+
+    dtype = torch.bfloat16
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rows_out = []
+    print(f"{'op S G D':>28} {'round':>5} {'(a) ms':>9} {'(b) ms':>9} "
+          f"{'(c) ms':>9} {'(b) GB/s':>9} {'(c) GB/s':>9}")
+    for S, G, D in GROUPED_SHAPES:
+        def new(*shape):
+            return torch.randn(*shape, device="cuda", generator=g).to(dtype)
+        # x alone exceeds the last-level cache; two buffers alternate
+        bufs = [(new(1, S, D), new(1, S, D)) for _ in range(2)]
+        mod = new(1, G, 6, D).unbind(-2)        # the caller's strided views
+        wide = [m.repeat_interleave(S // G, dim=1) for m in mod[:3]]
+        flat = [m[:, 0] for m in mod[:3]]
+        sides = {
+            "layer_norm_mod": (
+                lambda b: reference.layer_norm_mod(b[0], wide[0], wide[1]),
+                lambda b: ops.layer_norm_mod(b[0], flat[0], flat[1]),
+                lambda b: ops.layer_norm_mod(b[0], mod[0], mod[1]), 4),
+            "gate_residual": (
+                lambda b: reference.gate_residual(b[1], wide[2], b[0]),
+                lambda b: ops.gate_residual(b[1], flat[2], b[0]),
+                lambda b: ops.gate_residual(b[1], mod[2], b[0]), 6),
+        }
+        for op, (ref_fn, flat_fn, grp_fn, passes) in sides.items():
+            nbytes = passes * S * D
+            for r in range(args.rounds):
+                ta = time_op(ref_fn, bufs, max(args.iters // 10, 3))
+                tb = time_op(flat_fn, bufs, args.iters)
+                tc = time_op(grp_fn, bufs, args.iters)
+                row = dict(op=op, S=S, G=G, D=D, round=r, reference_ms=ta,
+                           flat_ms=tb, grouped_ms=tc,
+                           flat_gbs=nbytes / tb / 1e6,
+                           grouped_gbs=nbytes / tc / 1e6)
+                rows_out.append(row)
+                print(f"{op + f' {S} {G} {D}':>28} {r:>5} {ta:>9.4f} "
+                      f"{tb:>9.4f} {tc:>9.4f} {row['flat_gbs']:>9.0f} "
+                      f"{row['grouped_gbs']:>9.0f}", flush=True)
+        del bufs, mod, wide, flat, sides
+        torch.cuda.empty_cache()
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(rows_out, f, indent=1)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--dtype", default="fp16", choices=["bf16", "fp16"])
@@ -80,9 +141,15 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--shapes", default=SHAPES, metavar="op,rows,width;...")
     ap.add_argument("--json", default=None, help="write the rows here")
+    ap.add_argument("--grouped", action="store_true",
+                    help="time the grouped modulation kernels instead")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_token_ops.py measures on the GPU; none found")
+    if args.grouped:
+        assert ops.hip_available("layer_norm_mod_grouped"), \
+            "native extension missing"
+        return grouped(args)
     assert ops.hip_available("layer_norm_affine"), "native extension missing"
     dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
 
