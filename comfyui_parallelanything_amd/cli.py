@@ -59,6 +59,11 @@ def main(argv=None):
                     help="wan models: every token attends exactly the "
                          "frames BACK before to AHEAD after its own; BACK "
                          "may be 'all' (all,0 = frame-causal)")
+    ap.add_argument("--attn-top-p", type=float, default=None, metavar="P",
+                    help="wan models: per-head block-sparse self-attention "
+                         "over the key tiles holding mass P in (0, 1] of the "
+                         "mean-pooled scores (with --frame-window: plus the "
+                         "window's tiles)")
     ap.add_argument("--channels-last", action="store_true",
                     help="sd15 / sdxl: keep activations and conv weights "
                          "channels-last (NHWC GroupNorm kernels, token "
@@ -90,6 +95,13 @@ def main(argv=None):
                      "'all')")
         if frame_span[1] < 0 or (frame_span[0] or 0) < 0:
             ap.error("--frame-span values must be >= 0")
+    if args.attn_top_p is not None:
+        if not args.model.startswith("wan"):
+            ap.error("--attn-top-p applies to wan models only")
+        if not 0.0 < args.attn_top_p <= 1.0:
+            ap.error("--attn-top-p must lie in (0, 1]")
+        if frame_span is not None:
+            ap.error("--attn-top-p and --frame-span exclude each other")
     if args.channels_last and args.model not in ("sd15", "sdxl"):
         ap.error("--channels-last applies to sd15 and sdxl only")
     if args.token_ops and args.model not in ("sd15", "sdxl"):
@@ -124,6 +136,8 @@ def main(argv=None):
         model.cfg.self_attn_frame_window = args.frame_window
     if frame_span is not None:
         model.cfg.self_attn_frame_span = frame_span
+    if args.attn_top_p is not None:
+        model.cfg.self_attn_top_p = args.attn_top_p
 
     if args.lora:
         from .models.lora import merge_lora_file
@@ -176,6 +190,7 @@ def main(argv=None):
         "engine": "in-process", "text_len": text_len,
         "frame_window": args.frame_window,
         "frame_span": frame_span,
+        "attn_top_p": args.attn_top_p,
     }
     print(json.dumps(summary, indent=2))
     if args.json_out:

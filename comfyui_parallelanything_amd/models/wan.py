@@ -56,7 +56,7 @@ class WanBlock(nn.Module):
         self.ffn = FusedMLP(dim, ffn_dim, dim)
 
     def forward(self, x, e, context, pe, key_mask=None, block_mask=None,
-                self_attn=None, row_bounds=None):
+                self_attn=None, row_bounds=None, top_p=None, keep=None):
         # e: [B, 6, dim] time-modulation, or [B, f, 6, dim] with a timestep
         # per latent frame; learned bias added per block. The six views go
         # to the ops as they are: [B, dim], or [B, f, dim] rows of the
@@ -70,6 +70,10 @@ class WanBlock(nn.Module):
         # self_attn: optional (q, k, v, scale) -> [B,S,H,D] in place of the
         # local self-attention: x is a token shard and the keys live on other
         # ranks (parallel.sequence)
+        # top_p: optional float — the self-attention visits, per head and
+        # query block, the key tiles ops.select_block_mask picks from this
+        # block's own q and k (WanConfig.self_attn_top_p), OR-ed with the
+        # raw [nq, nk] block mask ``keep``
         m = (e + self.mod).unbind(dim=-2)  # 6 x [B, dim] or [B, f, dim]
         shift1, scale1, gate1, shift2, scale2, gate2 = m
 
@@ -81,6 +85,12 @@ class WanBlock(nn.Module):
             q, k, self.self_norm.query_norm.scale,
             self.self_norm.key_norm.scale, pe,
         )
+        if top_p is not None:
+            B, S, H, _ = q.shape
+            block_mask = ops.pack_head_block_mask(
+                ops.select_block_mask(q, k, top_p, bshd=True,
+                                      scale=self.scale, keep=keep),
+                B, H, S, S)
         if self_attn is None:
             attn = ops.attention_bshd(q, k, v, self.scale,
                                       block_mask=block_mask,
@@ -134,6 +144,14 @@ class WanConfig:
     # window. None, or a span that reaches every frame, is dense attention.
     # Not together with self_attn_frame_window.
     self_attn_frame_span: Optional[Tuple[Optional[int], int]] = None
+    # Top-p block-sparse self-attention, in (0, 1]: every block selects, per
+    # head and 256-token query block, the 64-token key tiles that hold this
+    # much of the softmax mass of the mean-pooled scores of its own q and k
+    # (ops.select_block_mask), packs them and attends those tiles only. With
+    # self_attn_frame_window the window's tiles are kept as well. None is
+    # the forward without it. Not with self_attn_frame_span or sequence
+    # parallelism. Nothing is claimed about image quality.
+    self_attn_top_p: Optional[float] = None
 
     @classmethod
     def wan22_a14b(cls) -> "WanConfig":
@@ -210,6 +228,36 @@ class WanDiT(nn.Module):
             self._mask_cache[key] = bm
         return bm
 
+    def _top_p_args(self, f, tokens_per_frame, device) -> dict:
+        """The blocks' ``top_p`` and ``keep`` for cfg.self_attn_top_p: keep
+        is the raw frame-window block mask when self_attn_frame_window is
+        set too (built once per (grid, window, device)), else None."""
+        cfg = self.cfg
+        if self._seq_parallel is not None:
+            raise ValueError(
+                "self_attn_top_p with sequence parallelism is not "
+                "supported: the ring has no block masks")
+        if cfg.self_attn_frame_span is not None:
+            raise ValueError(
+                "self_attn_top_p with self_attn_frame_span is not supported: "
+                "row bounds and block masks do not compose")
+        if not 0.0 < float(cfg.self_attn_top_p) <= 1.0:
+            raise ValueError(f"self_attn_top_p must lie in (0, 1], got "
+                             f"{cfg.self_attn_top_p}")
+        window = cfg.self_attn_frame_window
+        keep = None
+        if window is not None:
+            if window < 0:
+                raise ValueError(f"self_attn_frame_window must be >= 0, got "
+                                 f"{window}")
+            key = ("keep", f, tokens_per_frame, window, str(device))
+            keep = self._mask_cache.get(key)
+            if keep is None:
+                keep = ops.frame_window_block_mask(f, tokens_per_frame,
+                                                   window, device=device)
+                self._mask_cache[key] = keep
+        return {"top_p": float(cfg.self_attn_top_p), "keep": keep}
+
     def _frame_span_bounds(self, f, tokens_per_frame, device):
         """The packed self-attention RowBounds, or None for dense attention.
         Packed once per (grid, span, device)."""
@@ -280,6 +328,8 @@ class WanDiT(nn.Module):
                 raise ValueError(
                     "self_attn_frame_span with sequence parallelism is not "
                     "supported: the ring has no row bounds")
+            if cfg.self_attn_top_p is not None:
+                self._top_p_args(0, 0, x.device)    # raises
             x, timesteps, context, image_cond, attention_mask = sp.broadcast(
                 x, timesteps, context, image_cond, attention_mask)
         B, C, F, H, W = x.shape
@@ -332,7 +382,11 @@ class WanDiT(nn.Module):
         if attention_mask is not None:
             # packed once per forward, shared by every block's cross-attention
             mk["key_mask"] = context_key_mask(attention_mask, ctx)
-        bm = self._frame_window_mask(B, f, h * w, x.device)
+        if cfg.self_attn_top_p is not None:
+            mk.update(self._top_p_args(f, h * w, x.device))
+            bm = None
+        else:
+            bm = self._frame_window_mask(B, f, h * w, x.device)
         if bm is not None:
             mk["block_mask"] = bm
         rb = self._frame_span_bounds(f, h * w, x.device)

@@ -516,6 +516,11 @@ class BlockMask:
     On CPU only ``block`` and ``keys`` are set. ``live`` indexes ``words``
     and drives the kernel's global loads, so the pack kernel is its only
     producer: build one with pack_block_mask, never by hand.
+
+    The per-head form (pack_head_block_mask) holds ``block`` as bool [Bm, Hm,
+    nq, nk], Bm in {1, B}, Hm in {1, H}, ``live`` as [B, H, nq, nk], ``nlive``
+    as [B, H, nq] and the head count it was packed for in ``heads``, which
+    is 0 for the shared form.
     """
     block: torch.Tensor
     keys: Optional[torch.Tensor] = None
@@ -525,6 +530,7 @@ class BlockMask:
     batch: int = 0
     Sq: int = 0
     Sk: int = 0
+    heads: int = 0
 
 
 def pack_block_mask(block_mask, batch: int, Sq: int, Sk: int,
@@ -544,29 +550,139 @@ def pack_block_mask(block_mask, batch: int, Sq: int, Sk: int,
     """
     batch, Sq, Sk = int(batch), int(Sq), int(Sk)
     bm = reference.as_bool_block_mask(block_mask, Sq, Sk)
-    keys = None
-    if key_mask is not None:
-        keys = (key_mask.mask if isinstance(key_mask, KeyMask)
-                else reference.as_bool_key_mask(key_mask))
-        if tuple(keys.shape) != (batch, Sk):
-            raise ValueError(f"key mask {list(keys.shape)} does not match "
-                             f"[batch={batch}, Sk={Sk}]")
-        if keys.device != bm.device:
-            raise ValueError(f"key mask on {keys.device}, block mask on "
-                             f"{bm.device}")
+    keys = _block_mask_keys(key_mask, bm, batch, Sk)
     if bm.is_cuda:
         ext = _require_ext("pack_block_lists")
         if ext is not None:
-            if isinstance(key_mask, KeyMask) and key_mask.words is not None:
-                words = key_mask.words
-            else:
-                words = pack_key_mask(
-                    keys if keys is not None else
-                    torch.ones(batch, Sk, dtype=torch.bool,
-                               device=bm.device)).words
+            words = _block_mask_words(key_mask, keys, bm, batch, Sk)
             live, nlive = ext.pack_block_lists(bm, words)
             return BlockMask(bm, keys, words, live, nlive, batch, Sq, Sk)
     return BlockMask(bm, keys, batch=batch, Sq=Sq, Sk=Sk)
+
+
+def _block_mask_keys(key_mask, bm, batch: int, Sk: int):
+    """The bool [batch, Sk] key mask a block-mask pack composes with, or
+    None."""
+    if key_mask is None:
+        return None
+    keys = (key_mask.mask if isinstance(key_mask, KeyMask)
+            else reference.as_bool_key_mask(key_mask))
+    if tuple(keys.shape) != (batch, Sk):
+        raise ValueError(f"key mask {list(keys.shape)} does not match "
+                         f"[batch={batch}, Sk={Sk}]")
+    if keys.device != bm.device:
+        raise ValueError(f"key mask on {keys.device}, block mask on "
+                         f"{bm.device}")
+    return keys
+
+
+def _block_mask_words(key_mask, keys, bm, batch: int, Sk: int):
+    """pack_key_mask_kernel's words for a block-mask pack: the key mask's, or
+    those of an all-true mask."""
+    if isinstance(key_mask, KeyMask) and key_mask.words is not None:
+        return key_mask.words
+    return pack_key_mask(
+        keys if keys is not None else
+        torch.ones(batch, Sk, dtype=torch.bool, device=bm.device)).words
+
+
+def pack_head_block_mask(mask, B: int, H: int, Sq: int, Sk: int,
+                         key_mask=None) -> BlockMask:
+    """Pack a per-head block mask, bool/integer [Bm, Hm, ceil(Sq/256),
+    ceil(Sk/64)] with Bm in {1, B} and Hm in {1, H} (nonzero = query block qb
+    of head h of batch element b attends the key tile), for attention calls
+    of that batch size, head count and lengths. select_block_mask makes one
+    from q and k.
+
+    Contract, extending pack_block_mask's: key j is visible to query row i
+    of (b, h) iff mask[b or 0][h or 0][i // 256][j // 64] and (no key mask
+    or key_mask[b][j]). A row with no visible key returns zeros. K/V rows of
+    head h at keys that no query block of that (b, h) sees are don't-care,
+    NaN included. Floating masks raise; another shape raises ValueError. A
+    broadcast dimension is read through a zero stride, never expanded.
+
+    The result goes into ``block_mask=`` of ops.attention and
+    ops.attention_bshd (head dims 40 / 80 zero-padded on the latter, as for
+    the shared form). attention_bshd_split and the _lse ops raise
+    ValueError: there is no split or lse flavour."""
+    B, H, Sq, Sk = int(B), int(H), int(Sq), int(Sk)
+    bm = reference.as_bool_head_block_mask(mask, B, H, Sq, Sk)
+    keys = _block_mask_keys(key_mask, bm, B, Sk)
+    if bm.is_cuda:
+        ext = _require_ext("pack_head_block_lists")
+        if ext is not None:
+            words = _block_mask_words(key_mask, keys, bm, B, Sk)
+            live, nlive = ext.pack_head_block_lists(bm, words, H)
+            return BlockMask(bm, keys, words, live, nlive, B, Sq, Sk, H)
+    return BlockMask(bm, keys, batch=B, Sq=Sq, Sk=Sk, heads=H)
+
+
+SELECT_MAX_TILES = reference.SELECT_MAX_TILES   # key tiles per select call
+
+
+def select_block_mask(q, k, top_p: float, *, bshd: bool = False,
+                      scale: Optional[float] = None,
+                      keep=None) -> torch.Tensor:
+    """Per-head block mask from this call's q and k: bool [B, H,
+    ceil(Sq/256), ceil(Sk/64)] on q's device, for pack_head_block_mask or
+    ``block_mask=``. q and k are [B, H, S, D], or [B, S, H, D] with ``bshd``
+    (strided views are read in place).
+
+    Per (b, h, query block) the key tiles are scored by scale * <mean of the
+    block's query rows, mean of the tile's key rows> (rows inside Sq / Sk
+    only), softmaxed over the tiles, and tile t is selected iff the total
+    probability of the tiles scoring above it is < top_p: the shortest
+    descending prefix that reaches mass top_p, ties at the threshold all
+    kept. top_p lies in (0, 1]; 1 selects every tile and computes nothing.
+    ``keep``, an optional [nq, nk] bool/integer block mask (for example
+    frame_window_block_mask(frames, T, 0)), is OR-ed in afterwards.
+    reference.select_block_mask is the definition, in fp64.
+
+    On the GPU: bf16 / fp16, head dim 64 or 128 natively (other 16-bit head
+    dims up to 128 are zero-padded first, which leaves every score as it
+    is), rows starting on 16 bytes (RuntimeError otherwise), at most
+    SELECT_MAX_TILES key tiles; nothing is read on the host, so select, pack
+    and attention capture into one graph. ValueError: top_p outside (0, 1],
+    more key tiles than the cap, and on the GPU any other dtype or head dim
+    (there is no reference route there).
+
+    This is the mean-pool predictor of SpargeAttn without its
+    self-similarity gate. Nothing is claimed about image quality."""
+    s_ax, h_ax = (1, 2) if bshd else (2, 1)
+    reference.check_select(q, k, top_p, q.shape[s_ax] if q.dim() == 4 else 0,
+                           k.shape[s_ax] if k.dim() == 4 else 0)
+    B, H, D = q.shape[0], q.shape[h_ax], q.shape[3]
+    Sq, Sk = q.shape[s_ax], k.shape[s_ax]
+    if (k.shape[0], k.shape[h_ax], k.shape[3]) != (B, H, D):
+        raise ValueError(f"select_block_mask: k must have q's batch, heads "
+                         f"and head dim, got q {list(q.shape)}, k "
+                         f"{list(k.shape)}")
+    if k.device != q.device:
+        raise ValueError(f"select_block_mask: k on {k.device}, q on "
+                         f"{q.device}")
+    if keep is not None:
+        keep = reference.as_bool_block_mask(keep, Sq, Sk)
+        if keep.device != q.device:
+            raise ValueError(f"keep mask on {keep.device}, q on {q.device}")
+    scale = _softmax_scale(q, scale)
+    ext = _require_ext("select_block_mask") if q.is_cuda else None
+    if ext is not None:
+        if q.dtype not in _NATIVE16 or k.dtype != q.dtype or D > 128:
+            raise ValueError(
+                f"select_block_mask on the GPU takes bf16 or fp16 q and k of "
+                f"one dtype and head dim <= 128, got {q.dtype}, {k.dtype}, "
+                f"D={D}")
+        nq, nk = reference.block_mask_shape(Sq, Sk)
+        if float(top_p) == 1.0 or nq == 0 or nk == 0:
+            return torch.ones(B, H, nq, nk, dtype=torch.bool, device=q.device)
+        if D not in (64, 128):
+            width = 64 if D <= 64 else 128
+            q, k = (torch.nn.functional.pad(t, (0, width - D))
+                    for t in (q, k))
+        return ext.select_block_mask(q, k, float(top_p), scale, bshd, keep)
+    if bshd:
+        q, k = q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3)
+    return reference.select_block_mask(q, k, top_p, scale, keep)
 
 
 def frame_window_block_mask(frames: int, tokens_per_frame: int, window: int,
@@ -599,7 +715,8 @@ def frame_window_block_mask(frames: int, tokens_per_frame: int, window: int,
             & (klo[None, :] <= qhi[:, None] + window))
 
 
-def _block_mask_for(block_mask, key_mask, q, Sq: int, Sk: int) -> BlockMask:
+def _block_mask_for(block_mask, key_mask, q, Sq: int, Sk: int,
+                    H: int) -> BlockMask:
     B = q.shape[0]
     if not isinstance(block_mask, BlockMask):
         if block_mask.device != q.device:
@@ -607,6 +724,8 @@ def _block_mask_for(block_mask, key_mask, q, Sq: int, Sk: int) -> BlockMask:
                              f"{q.device}")
         if key_mask is not None:
             key_mask = _key_mask_for(key_mask, q)
+        if block_mask.dim() == 4:
+            return pack_head_block_mask(block_mask, B, H, Sq, Sk, key_mask)
         return pack_block_mask(block_mask, B, Sq, Sk, key_mask)
     if key_mask is not None:
         raise ValueError("a packed BlockMask takes no separate key_mask=: "
@@ -617,11 +736,15 @@ def _block_mask_for(block_mask, key_mask, q, Sq: int, Sk: int) -> BlockMask:
         raise ValueError(
             f"BlockMask was packed for (B, Sq, Sk) = "
             f"{(bm.batch, bm.Sq, bm.Sk)}, this call has {(B, Sq, Sk)}")
+    if bm.heads and bm.heads != H:
+        raise ValueError(f"BlockMask was packed for {bm.heads} heads, this "
+                         f"call has {H}")
     if bm.block.device != q.device:
         raise ValueError(f"block mask on {bm.block.device}, q on {q.device}")
     if q.is_cuda and bm.live is None:
         # packed on CPU (or under PA_ALLOW_EAGER) and moved: pack here
-        bm = pack_block_mask(bm.block, B, Sq, Sk, bm.keys)
+        bm = (pack_head_block_mask(bm.block, B, H, Sq, Sk, bm.keys)
+              if bm.heads else pack_block_mask(bm.block, B, Sq, Sk, bm.keys))
     return bm
 
 
@@ -812,9 +935,10 @@ _NO_ATTN_MASK_LSE = ("attn_mask= is not supported together with the "
 
 
 def _mask_for(key_mask, block_mask, q, Sq: int, Sk: int, row_bounds=None,
-              attn_mask=None):
+              attn_mask=None, H: int = 0):
     """The call's packed mask: None, a KeyMask, a BlockMask (which holds
-    the key mask too), a RowBounds or an AttnMask."""
+    the key mask too), a RowBounds or an AttnMask. H: the call's head
+    count, which a per-head block mask is checked against."""
     if attn_mask is not None:
         if not (key_mask is None and block_mask is None
                 and row_bounds is None):
@@ -827,7 +951,7 @@ def _mask_for(key_mask, block_mask, q, Sq: int, Sk: int, row_bounds=None,
                 f"attention: {reference.NO_ROW_BOUNDS_WITH_MASK}")
         return _row_bounds_for(row_bounds, q, Sq, Sk)
     if block_mask is not None:
-        return _block_mask_for(block_mask, key_mask, q, Sq, Sk)
+        return _block_mask_for(block_mask, key_mask, q, Sq, Sk, H)
     return None if key_mask is None else _key_mask_for(key_mask, q)
 
 
@@ -899,7 +1023,8 @@ def _attn_native(q, k, v, scale: float, km, bshd: bool,
 
     Picks ext.attn_fwd[_bshd][_split][_lse][_masked]; ``km`` is None, a
     KeyMask, a BlockMask, whose 3-D ``live`` selects the block-list
-    kernels inside the masked entry points, a RowBounds, which has the
+    kernels inside the masked entry points and whose 4-D ``live`` their
+    per-head flavour, a RowBounds, which has the
     _band entry points, or an AttnMask, which has the _bits ones."""
     band, bits = isinstance(km, RowBounds), isinstance(km, AttnMask)
     name = _attn_op(bshd, split, lse) + (
@@ -941,7 +1066,12 @@ def _attention(q, k, v, scale, key_mask, block_mask, *, bshd: bool,
     kernels, else note the gap and take the reference path."""
     Sq, Sk = _check_qkv(q, k, v, bshd=bshd, split=split)
     scale = _softmax_scale(q, scale)
-    km = _mask_for(key_mask, block_mask, q, Sq, Sk, row_bounds, attn_mask)
+    km = _mask_for(key_mask, block_mask, q, Sq, Sk, row_bounds, attn_mask,
+                   H=q.shape[2 if bshd else 1])
+    if isinstance(km, BlockMask) and km.heads and split is not None:
+        raise ValueError("attention_bshd_split: per-head block masks have "
+                         "no split flavour (attention and attention_bshd "
+                         "take them)")
     why = None
     if q.is_cuda:
         res, why = _attn_native(q, k, v, scale, km, bshd, split, lse)
@@ -984,7 +1114,10 @@ def attention(q, k, v, scale: Optional[float] = None,
     block_mask: optional BlockMask or raw [ceil(Sq/256), ceil(Sk/64)]
     bool/integer mask (see pack_block_mask for the contract). A raw one is
     packed per call, together with key_mask; a packed one already holds its
-    key mask, and passing key_mask= beside it raises.
+    key mask, and passing key_mask= beside it raises. The per-head form, a
+    raw [Bm, Hm, nq, nk] mask (Bm in {1, B}, Hm in {1, H}) or what
+    pack_head_block_mask returns, goes here too (see pack_head_block_mask
+    and select_block_mask); attention_bshd_split refuses it.
     row_bounds: optional RowBounds or raw (lo, hi) pair of [Sq] integer
     tensors, query row i seeing the keys lo[i] <= j < hi[i] (see
     pack_row_bounds for the contract; causal_row_bounds and

@@ -199,6 +199,96 @@ std::vector<at::Tensor> pack_block_lists(at::Tensor block, at::Tensor words) {
 }
 
 // ---------------------------------------------------------------------------
+// Per-head block-mask pack: [Bm, Hm, nq, nk] bool block mask, Bm in {1, B},
+// Hm in {1, H} (a broadcast dimension is a zero stride here, never an expanded
+// copy) plus the key-mask words -> one live list per (b, h, qb), which the
+// HLIST attention instantiations read.
+//   live[b][h][qb][..]  ascending tiles t with block[b|0][h|0][qb][t] != 0
+//                       and words[b][t] != 0, compacted to the front (zero
+//                       tail)
+//   nlive[b][h][qb]     how many
+// pack_block_lists_kernel with the head in the row: one wave per (qb, h, b),
+// the same ballot + prefix popcount, the same dropped all-dead tiles, no host
+// read.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void pack_head_block_lists_kernel(
+    const unsigned char* __restrict__ block, long m_bs, long m_hs,
+    const unsigned long long* __restrict__ words, int* __restrict__ live,
+    int* __restrict__ nlive, int nq, int n_tiles) {
+    const int qb = blockIdx.x;
+    const int h = blockIdx.y;
+    const int b = blockIdx.z;
+    const int lane = threadIdx.x;
+    const unsigned char* bm =
+        block + b * m_bs + h * m_hs + (long)qb * n_tiles;
+    const unsigned long long* wb = words + (long)b * n_tiles;
+    const long row = ((long)b * gridDim.y + h) * nq + qb;
+    int* lb = live + row * n_tiles;
+    int count = 0;
+    for (int base = 0; base < n_tiles; base += 64) {
+        const int t = base + lane;
+        const bool alive = t < n_tiles && bm[t] != 0 && wb[t] != 0ull;
+        const unsigned long long m = __ballot(alive);
+        if (alive)
+            lb[count + __popcll(m & ((1ull << lane) - 1ull))] = t;
+        count += __popcll(m);
+    }
+    for (int i = count + lane; i < n_tiles; i += 64) lb[i] = 0;
+    if (lane == 0) nlive[row] = count;
+}
+
+// block: [Bm, Hm, nq, nk] bool/integer, Bm in {1, B}, Hm in {1, H}; words:
+// [B, nk] from pack_key_mask.
+std::vector<at::Tensor> pack_head_block_lists(at::Tensor block,
+                                              at::Tensor words, long H) {
+    CHECK_GPU(block);
+    CHECK_GPU(words);
+    TORCH_CHECK(block.dim() == 4,
+                "pack_head_block_lists expects a [Bm, Hm, nq, nk] block mask");
+    TORCH_CHECK(block.scalar_type() == at::kBool ||
+                    at::isIntegralType(block.scalar_type(), false),
+                "pack_head_block_lists: bool or integer block mask only "
+                "(nonzero = attend); additive float biases are not "
+                "supported, got ", block.scalar_type());
+    TORCH_CHECK(words.device() == block.device(),
+                "pack_head_block_lists: words must be on the block mask's "
+                "device");
+    TORCH_CHECK(words.dim() == 2 && words.scalar_type() == at::kLong &&
+                    words.is_contiguous(),
+                "pack_head_block_lists: words must be contiguous [B, nk] "
+                "int64 (pack_key_mask's)");
+    TORCH_CHECK(words.size(1) == block.size(3),
+                "pack_head_block_lists: block mask has ", block.size(3),
+                " key tiles, words have ", words.size(1));
+    const int B = (int)words.size(0);
+    TORCH_CHECK((block.size(0) == 1 || block.size(0) == B) &&
+                    (block.size(1) == 1 || block.size(1) == H),
+                "pack_head_block_lists: block mask batch and heads must be 1 "
+                "or (B, H) = (", B, ", ", H, "), got ", block.sizes());
+    TORCH_CHECK(B <= 65535 && H <= 65535,
+                "pack_head_block_lists: batch ", B, " or heads ", H,
+                " exceeds 65535");
+    auto bm = block.scalar_type() == at::kBool ? block : block.ne(0);
+    const int nq = (int)bm.size(2), n_tiles = (int)bm.size(3);
+    // each [nq, nk] plane dense; the two leading strides are taken as they
+    // are, 0 for a dimension of size 1
+    if (bm.stride(3) != 1 || bm.stride(2) != n_tiles) bm = bm.contiguous();
+    auto live = at::empty({B, H, nq, n_tiles}, bm.options().dtype(at::kInt));
+    auto nlive = at::empty({B, H, nq}, bm.options().dtype(at::kInt));
+    if (B > 0 && H > 0 && nq > 0)
+        hipLaunchKernelGGL(pack_head_block_lists_kernel,
+                           dim3((unsigned)nq, (unsigned)H, (unsigned)B),
+                           dim3(64), 0, cur_stream(),
+                           (const unsigned char*)bm.data_ptr(),
+                           bm.size(0) == 1 ? 0L : (long)bm.stride(0),
+                           bm.size(1) == 1 ? 0L : (long)bm.stride(1),
+                           (const unsigned long long*)words.data_ptr(),
+                           live.data_ptr<int>(), nlive.data_ptr<int>(), nq,
+                           n_tiles);
+    return {live, nlive};
+}
+
+// ---------------------------------------------------------------------------
 // Row-bounds pack: lo, hi [Sq] int64 (query row i sees keys lo[i] <= j <
 // hi[i], shared by batch and heads) -> what the BAND attention instantiations
 // read.
@@ -466,6 +556,15 @@ std::vector<at::Tensor> pack_attn_mask(at::Tensor mask) {
 // is block-uniform, so everything above holds unchanged; the mask words stay
 // per batch element. Nothing else differs from MASKED.
 //
+// HLIST (per-head block masks, needs QLIST; see pack_head_block_lists_kernel):
+// the list belongs to (batch element, head, query block): row (b * H + h) *
+// nq + qtile of live/nlive. h is block-uniform in both grid decodes, as qtile
+// is, so trip counts and barriers stay uniform; the mask words stay per batch
+// element. The kernel holds the count inside [0, n_tiles] and every entry
+// inside [0, n_tiles) itself, so no K/V address depends on what the list
+// holds. Nothing else differs from QLIST, and every instantiation without the
+// flag compiles to the code it had before the flag existed.
+//
 // LSE (ring / chunked attention, see attn_merge.h): the epilogue also stores
 // the row's natural-log sum over its visible keys of exp(scale * q.k), as
 // fp32 ln2 * (m_run + log2(l_run)), and -inf for a row that saw no key
@@ -524,7 +623,8 @@ std::vector<at::Tensor> pack_attn_mask(at::Tensor mask) {
 // over the mx = -3e30 floor, and the instantiations are built and rounded
 // the way BAND's are.
 template <int D, typename E, bool MASKED = false, bool QLIST = false,
-          bool LSE = false, int DH = D, bool BAND = false, bool BITS = false>
+          bool LSE = false, int DH = D, bool BAND = false, bool BITS = false,
+          bool HLIST = false>
 __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     const E* __restrict__ q, const E* __restrict__ k,
     const E* __restrict__ v, E* __restrict__ out,
@@ -556,6 +656,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
                   "row bounds: plain flavour of the two tile classes only");
     static_assert(!BITS || (!MASKED && !QLIST && !LSE && DH == D && !BAND),
                   "dense masks: plain flavour of the two tile classes only");
+    static_assert(!HLIST || (MASKED && QLIST && !LSE && DH == D),
+                  "per-head lists: block-list flavour of the two tile classes");
     constexpr int KK = (DH + 15) / 16;   // QK^T K-steps per 32-key tile
     constexpr int NV = (DH + 31) / 32;   // PV dim tiles
     constexpr int GROW = DH / 8;         // 16-byte granules per K/V row
@@ -879,7 +981,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     // the masked and unmasked instantiations share it:
     //   nt          trip count: nlive[b] (MASKED) or n_tiles
     //   tile_at(j)  j-th tile to process: live[b][j] (MASKED) or j
-    // (QLIST: read nlive[b][qtile] and live[b][qtile][j] for these two)
+    // (QLIST: read nlive[b][qtile] and live[b][qtile][j] for these two;
+    // HLIST: nlive[b][h][qtile] and live[b][h][qtile][j], held in range)
     //   word_of(t)  tile t's 64-bit mask word (MASKED) or 0 (ignored)
     // (BAND: the block's t1 - t0 and t0 + j, read before the phases above)
     // (BITS: the list of (bm, query block), whose entries tile_no() strips of
@@ -894,6 +997,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     // row of live/nlive: per batch element, or per (b, query block)
     const long lrow =
         BITS ? b * bits_bstride * ((S + WAVES * 32 - 1) / (WAVES * 32)) + qtile
+        : HLIST ? bh * ((S + WAVES * 32 - 1) / (WAVES * 32)) + qtile
         : QLIST ? b * ((S + WAVES * 32 - 1) / (WAVES * 32)) + qtile : b;
     const int* live_b =
         (MASKED || BITS) ? mask_live + lrow * n_tiles : nullptr;
@@ -902,8 +1006,9 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
         : MASKED ? mask_words + b * n_tiles : nullptr;
     const int nt =
         BAND ? band_nt
-        : BITS ? min(max(__builtin_amdgcn_readfirstlane(mask_nlive[lrow]), 0),
-                     n_tiles)
+        : (BITS || HLIST)
+            ? min(max(__builtin_amdgcn_readfirstlane(mask_nlive[lrow]), 0),
+                  n_tiles)
         : MASKED ? __builtin_amdgcn_readfirstlane(mask_nlive[lrow]) : n_tiles;
     // BITS: this lane's words, bits[bm][tile][row]; rows at or beyond S take
     // the clamped row of the Q load (never stored)
@@ -917,6 +1022,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_v4_kernel(
     auto row_word = [&](int tile) PA_INL { return rowp[(long)tile * S]; };
     auto tile_no = [&](int e) PA_INL {
         if constexpr (BITS) return min(e & (PA_BITS_FULL - 1), n_tiles - 1);
+        else if constexpr (HLIST) return min(max(e, 0), n_tiles - 1);
         else return e;
     };
     auto tile_at = [&](int j) PA_INL {
@@ -1137,7 +1243,8 @@ PA_ATTN_BAND_BITS(128, _Float16)
 
 // Packed key mask as the MASKED kernels take it (see pack_key_mask). With a
 // block mask, live is [B, nq, nk] and nlive [B, nq] (see pack_block_lists),
-// which selects the QLIST instantiations.
+// which selects the QLIST instantiations; with a per-head block mask, [B, H,
+// nq, nk] and [B, H, nq] (see pack_head_block_lists), which selects HLIST.
 struct AttnKeyMask {
     at::Tensor words, live, nlive;
 };
@@ -1206,12 +1313,13 @@ std::vector<long> attn_native_head_dims() {
 }
 
 template <int D, bool MASKED, bool QLIST, bool LSE, int DH,
-          bool BAND = false, bool BITS = false>
+          bool BAND = false, bool BITS = false, bool HLIST = false>
 static void launch_attn_v4_as(at::ScalarType st, dim3 grid,
                               const AttnArgs& a) {
     PA_WITH_ELEM16(st, hipLaunchKernelGGL(
         HIP_KERNEL_NAME(
-            attn_fwd_v4_kernel<D, E, MASKED, QLIST, LSE, DH, BAND, BITS>),
+            attn_fwd_v4_kernel<D, E, MASKED, QLIST, LSE, DH, BAND, BITS,
+                               HLIST>),
         grid, dim3(512), 0,
         cur_stream(), (const E*)a.q, (const E*)a.k, (const E*)a.v, (E*)a.out,
         a.S, a.Sk, a.scale, a.H, a.q_bs, a.q_hs, a.q_ss, a.k_bs, a.k_hs,
@@ -1239,7 +1347,9 @@ static void launch_attn_v4(int D, at::ScalarType st, dim3 grid,
 
 // The one attention launcher. has_split (bshd only) writes rows >= split to
 // a second tensor, 0 < split < S; km != nullptr selects the MASKED
-// instantiations, and a 3-D km->live their QLIST flavour. want_lse appends
+// instantiations, a 3-D km->live their QLIST flavour and a 4-D one ([B, H,
+// nq, nk], see pack_head_block_lists) their HLIST flavour, which exists at
+// head dims 64 and 128 without a split. want_lse appends
 // the fp32 log-sum-exp, in the output's layout without D, to the result; it
 // goes with neither a split nor a block mask. band != nullptr selects the
 // BAND instantiations: head dims 64 and 128, and nothing of the above.
@@ -1282,11 +1392,13 @@ static std::vector<at::Tensor> attn_fwd_launch(
                 "attn_fwd: v must have k's length (", k.size(s_ax),
                 " keys), got ", v.size(s_ax));
     TORCH_CHECK(!want_lse || (!has_split &&
-                              (km == nullptr || km->live.dim() != 3)),
+                              (km == nullptr || km->live.dim() < 3)),
                 "attn_fwd: the log-sum-exp output goes with neither a split "
                 "nor a block mask");
+    TORCH_CHECK(!has_split || km == nullptr || km->live.dim() != 4,
+                "attn_fwd: per-head block lists have no split flavour");
     TORCH_CHECK(D == cls || (!has_split && !want_lse &&
-                             (km == nullptr || km->live.dim() != 3)),
+                             (km == nullptr || km->live.dim() < 3)),
                 "attn_fwd: head dim ", D, " runs the plain and key-masked "
                 "kernels only; zero-pad to ", cls, " for a split, the "
                 "log-sum-exp or a block mask");
@@ -1340,14 +1452,15 @@ static std::vector<at::Tensor> attn_fwd_launch(
                         km->nlive.scalar_type() == at::kInt,
                     "attn_fwd: key mask needs int64 words, int32 live/nlive");
         const bool qlist = km->live.dim() == 3;
+        const bool hlist = km->live.dim() == 4;
         TORCH_CHECK(km->words.dim() == 2 &&
-                        (km->live.dim() == 2 || km->live.dim() == 3) &&
+                        (km->live.dim() == 2 || qlist || hlist) &&
                         km->nlive.dim() == km->live.dim() - 1 &&
                         km->words.size(0) == B && km->live.size(0) == B &&
                         km->nlive.size(0) == B,
                     "attn_fwd: key mask batch must equal q's batch (", B, ")");
         TORCH_CHECK(km->words.size(1) == n_tiles &&
-                        km->live.size(qlist ? 2 : 1) == n_tiles,
+                        km->live.size(km->live.dim() - 1) == n_tiles,
                     "attn_fwd: key mask was packed for another Sk (", Sk,
                     " keys need ", n_tiles, " tiles, got ",
                     km->words.size(1), ")");
@@ -1357,6 +1470,18 @@ static std::vector<at::Tensor> attn_fwd_launch(
                         "attn_fwd: block mask was packed for another Sq (", S,
                         " rows need ", nqb, " query blocks, got ",
                         km->live.size(1), ")");
+        }
+        if (hlist) {
+            // what the kernel indexes: row (b * H + h) * nq + qtile
+            const long nqb = (S + 255) / 256;
+            TORCH_CHECK(km->live.size(1) == H && km->nlive.size(1) == H,
+                        "attn_fwd: per-head block mask was packed for "
+                        "another head count (q has ", H, ", got ",
+                        km->live.size(1), ")");
+            TORCH_CHECK(km->live.size(2) == nqb && km->nlive.size(2) == nqb,
+                        "attn_fwd: block mask was packed for another Sq (", S,
+                        " rows need ", nqb, " query blocks, got ",
+                        km->live.size(2), ")");
         }
         TORCH_CHECK(km->words.is_contiguous() && km->live.is_contiguous() &&
                         km->nlive.is_contiguous(),
@@ -1497,7 +1622,14 @@ static std::vector<at::Tensor> attn_fwd_launch(
         else launch_attn_v4<false, false, true>(D, st, grid, a);
         return {out, lse};
     }
-    if (km != nullptr && km->live.dim() == 3)
+    if (km != nullptr && km->live.dim() == 4) {
+        if (D == 64)
+            launch_attn_v4_as<64, true, true, false, 64, false, false, true>(
+                st, grid, a);
+        else
+            launch_attn_v4_as<128, true, true, false, 128, false, false,
+                              true>(st, grid, a);
+    } else if (km != nullptr && km->live.dim() == 3)
         launch_attn_v4<true, true>(D, st, grid, a);
     else if (km != nullptr)
         launch_attn_v4<true>(D, st, grid, a);

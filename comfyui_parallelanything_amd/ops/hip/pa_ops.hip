@@ -29,6 +29,7 @@
 #include "fp8.h"
 #include "attention.h"
 #include "attn_merge.h"
+#include "block_select.h"
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rms_norm", &rms_norm, "RMSNorm (gfx950)",
@@ -74,6 +75,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("pack_block_lists", &pack_block_lists,
           "[nq,nk] block mask + key-mask words -> per-(b, q-block) live "
           "tile lists [B,nq,nk] and counts [B,nq]");
+    m.def("pack_head_block_lists", &pack_head_block_lists,
+          "[Bm,Hm,nq,nk] per-head block mask (Bm in {1,B}, Hm in {1,H}) + "
+          "key-mask words -> per-(b, h, q-block) live tile lists "
+          "[B,H,nq,nk] and counts [B,H,nq]",
+          py::arg("block"), py::arg("words"), py::arg("heads"));
+    m.def("select_block_mask", &select_block_mask,
+          "Top-p key tiles per (b, h, q-block) from the block means of q and "
+          "k -> bool [B,H,nq,nk] (gfx950)",
+          py::arg("q"), py::arg("k"), py::arg("top_p"), py::arg("scale"),
+          py::arg("bshd") = false, py::arg("keep") = py::none());
     m.def("pack_row_bounds", &pack_row_bounds,
           "[Sq] integer row bounds lo, hi -> (clamped lo_c, hi_c, per-query-"
           "block tile range [nq,4])",

@@ -289,6 +289,109 @@ def as_bool_block_mask(mask: torch.Tensor, Sq: int, Sk: int) -> torch.Tensor:
     return mask if mask.dtype == torch.bool else mask != 0
 
 
+def as_bool_head_block_mask(mask: torch.Tensor, B: int, H: int, Sq: int,
+                            Sk: int) -> torch.Tensor:
+    """[Bm, Hm, ceil(Sq/256), ceil(Sk/64)] bool/integer per-head block mask,
+    Bm in {1, B}, Hm in {1, H} (nonzero = query block qb of head h of batch
+    element b attends the key tile) -> bool. Floating masks are refused for
+    as_bool_key_mask's reason; another shape raises ValueError."""
+    if mask.dtype.is_floating_point or mask.dtype.is_complex:
+        raise ValueError(
+            f"block mask must be bool or integer (nonzero = attend), got "
+            f"{mask.dtype}: additive float biases are not supported")
+    nq, nk = block_mask_shape(Sq, Sk)
+    if (mask.dim() != 4 or mask.shape[0] not in (1, B)
+            or mask.shape[1] not in (1, H)
+            or tuple(mask.shape[2:]) != (nq, nk)):
+        raise ValueError(
+            f"per-head block mask must be [Bm, Hm, ceil(Sq/{Q_BLOCK}), "
+            f"ceil(Sk/{KV_TILE})] = [1 or {B}, 1 or {H}, {nq}, {nk}] for "
+            f"B={B}, H={H}, Sq={Sq}, Sk={Sk}, got {list(mask.shape)}")
+    return mask if mask.dtype == torch.bool else mask != 0
+
+
+# Key tiles select_block_mask takes: what one select block of the native
+# kernel holds in LDS (ops/hip/block_select.h). 3072 tiles = 196 608 keys.
+SELECT_MAX_TILES = 3072
+
+
+def _block_means(x: torch.Tensor, rows: int) -> torch.Tensor:
+    """[B, H, S, D] -> fp64 [B, H, ceil(S/rows), D]: the mean of each block
+    of ``rows`` rows, the last one over its rows < S only."""
+    B, H, S, D = x.shape
+    n = (S + rows - 1) // rows
+    xd = torch.nn.functional.pad(x.double(), (0, 0, 0, n * rows - S))
+    count = torch.full((n,), rows, dtype=torch.float64, device=x.device)
+    if n:
+        count[-1] = S - (n - 1) * rows
+    return xd.view(B, H, n, rows, D).sum(3) / count[:, None]
+
+
+def select_scores(q, k, scale: Optional[float] = None):
+    """(s, p) of select_block_mask, fp64 [B, H, nq, nk]: the scaled scores of
+    the block means and their softmax over the key tiles."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    qbar = _block_means(q, Q_BLOCK)
+    kbar = _block_means(k, KV_TILE)
+    # a product and a sum per tile, not a matmul: a blocked matmul adds the D
+    # terms in an order that depends on the column, so two tiles with the
+    # same kbar could differ in the last bit and stop being a tie
+    s = scale * torch.stack(
+        [(qbar[:, :, i, None, :] * kbar).sum(-1)
+         for i in range(qbar.shape[2])], dim=2)
+    return s, torch.softmax(s, dim=-1)
+
+
+def check_select(q, k, top_p, Sq: int, Sk: int):
+    """What select_block_mask takes, on every device."""
+    if not (q.dim() == 4 and k.dim() == 4):
+        raise ValueError(f"select_block_mask expects 4-D q/k, got "
+                         f"{q.dim()}-D, {k.dim()}-D")
+    if not 0.0 < float(top_p) <= 1.0:
+        raise ValueError(f"select_block_mask: top_p must lie in (0, 1], got "
+                         f"{top_p}")
+    nk = block_mask_shape(Sq, Sk)[1]
+    if nk > SELECT_MAX_TILES:
+        raise ValueError(
+            f"select_block_mask: Sk={Sk} is {nk} key tiles, above the cap of "
+            f"{SELECT_MAX_TILES} ({SELECT_MAX_TILES * KV_TILE} keys)")
+
+
+def select_block_mask(q, k, top_p: float, scale: Optional[float] = None,
+                      keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Top-p key tiles per (batch element, head, query block), in fp64: q
+    [B, H, Sq, D], k [B, H, Sk, D] -> bool [B, H, ceil(Sq/256), ceil(Sk/64)].
+
+    qbar[b, h, qb] is the mean of the block's query rows < Sq, kbar[b, h, t]
+    the mean of the tile's key rows < Sk, s_t = scale * <qbar, kbar_t> and p
+    its softmax over t. Tile t is selected iff the total p of the tiles with
+    s_u > s_t is < top_p: the shortest descending prefix that reaches mass
+    top_p, with ties at the threshold all kept. top_p = 1 selects every tile
+    (no summation). ``keep``, an optional [nq, nk] bool/integer block mask,
+    is OR-ed in afterwards. This is the mean-pool predictor of SpargeAttn
+    without its self-similarity gate; nothing is claimed about quality."""
+    Sq, Sk = q.shape[2], k.shape[2]
+    check_select(q, k, top_p, Sq, Sk)
+    B, H = q.shape[:2]
+    nq, nk = block_mask_shape(Sq, Sk)
+    if float(top_p) == 1.0 or nq == 0 or nk == 0:
+        sel = torch.ones(B, H, nq, nk, dtype=torch.bool, device=q.device)
+    else:
+        s, p = select_scores(q, k, scale)
+        # mass above s_t: the suffix sum of p in ascending order of s, from
+        # the first entry greater than s_t
+        s_asc, order = torch.sort(s, dim=-1)
+        suffix = torch.flip(torch.cumsum(
+            torch.flip(torch.gather(p, -1, order), (-1,)), -1), (-1,))
+        suffix = torch.nn.functional.pad(suffix, (0, 1))
+        first_above = torch.searchsorted(s_asc, s, right=True)
+        sel = torch.gather(suffix, -1, first_above) < float(top_p)
+    if keep is not None:
+        sel = sel | as_bool_block_mask(keep, Sq, Sk).to(q.device)
+    return sel
+
+
 def check_row_bounds(lo, hi, Sq: int):
     """lo, hi: two [Sq] integer tensors (query row i sees the keys lo[i] <=
     j < hi[i]). Floating and bool tensors are refused for as_bool_key_mask's
@@ -401,7 +504,10 @@ def attention(
     block_mask[i // 256][j // 64] and (no key mask or key_mask[b][j]). K/V
     rows at keys no query row of that batch element sees are don't-care
     (zeroed before the matmuls), and a query row with no visible key gives
-    zeros.
+    zeros. The per-head form is [Bm, Hm, ceil(Sq/256), ceil(Sk/64)] with Bm
+    in {1, B} and Hm in {1, H}: block_mask[b or 0][h or 0][i // 256][j // 64]
+    under the same contract, K/V rows of head h at keys no query row of that
+    (b, h) sees being don't-care.
 
     row_bounds: optional (lo, hi), two [Sq] integer tensors shared by batch
     and heads. Key j is visible to query row i iff lo[i] <= j < hi[i] and
@@ -438,7 +544,12 @@ def attention(
     # vis: which keys each query row sees, broadcast over [B, H, Sq, Sk];
     # None = all of them
     vis = None
-    if block_mask is not None:
+    if block_mask is not None and block_mask.dim() == 4:
+        bm = as_bool_head_block_mask(block_mask, B, q.shape[1], Sq,
+                                     Sk).to(q.device)
+        vis = bm.repeat_interleave(Q_BLOCK, dim=2).repeat_interleave(
+            KV_TILE, dim=3)[:, :, :Sq, :Sk]             # [Bm, Hm, Sq, Sk]
+    elif block_mask is not None:
         bm = as_bool_block_mask(block_mask, Sq, Sk).to(q.device)
         vis = bm.repeat_interleave(Q_BLOCK, dim=0).repeat_interleave(
             KV_TILE, dim=1)[None, None, :Sq, :Sk]       # [1, 1, Sq, Sk]

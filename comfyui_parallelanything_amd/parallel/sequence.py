@@ -201,6 +201,9 @@ def install_sequence_parallel(model, info: DistInfo, group=None):
     if model.cfg.self_attn_frame_window is not None:
         raise ValueError("self_attn_frame_window with sequence parallelism "
                          "is not supported: the ring has no block masks")
+    if model.cfg.self_attn_top_p is not None:
+        raise ValueError("self_attn_top_p with sequence parallelism is not "
+                         "supported: the ring has no block masks")
     if not 1 <= info.world_size <= ops.ATTN_MERGE_MAX:
         raise ValueError(f"sequence parallelism over 1 to "
                          f"{ops.ATTN_MERGE_MAX} ranks, got {info.world_size}")

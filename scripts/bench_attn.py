@@ -21,7 +21,12 @@ H40 D128 over S = F x 3600 tokens (F = 21 gives 75 600). --block-mask
 (with the key mask, if any): full = every block live (the block-list
 kernel's overhead against --key-mask full), frame:W = the frame window of
 ops.frame_window_block_mask (needs --frames). The mask density — live
-256x64 blocks over all blocks — is printed beside each time.
+256x64 blocks over all blocks — is printed beside each time. topp:P runs the
+per-head kernels on ops.select_block_mask(q, k, P) of the call's own q and k
+(no key mask): select + pack are timed on their own and printed beside the
+density and the attention time. The data is random, so the pooled scores are
+near-uniform and the density comes out near P. full4d = the per-head kernels
+on an all-true [1, 1, nq, nk] mask (their price against `full`).
 
 --row-bounds {causal,frame:B,A} runs the row-bounds kernels instead (no key
 or block mask, no --lse): causal = ops.causal_row_bounds, frame:B,A = ops.
@@ -118,7 +123,8 @@ def main():
                     default="none")
     ap.add_argument("--live-keys", type=int, default=64,
                     help="live keys per batch element for --key-mask lens")
-    ap.add_argument("--block-mask", default="none", metavar="none|full|frame:W")
+    ap.add_argument("--block-mask", default="none",
+                    metavar="none|full|full4d|frame:W|topp:P")
     ap.add_argument("--row-bounds", default="none",
                     metavar="none|causal|frame:B,A")
     ap.add_argument("--attn-mask", default="none",
@@ -140,13 +146,19 @@ def main():
             ap.error("--shape takes B,H,Sq,Sk,D")
     if args.lse and args.block_mask != "none":
         ap.error("--lse takes no block mask")
-    window = None
+    window = top_p = None
     if args.block_mask.startswith("frame:"):
         window = int(args.block_mask.split(":", 1)[1])
         if args.frames <= 0:
             ap.error("--block-mask frame:W needs --frames")
-    elif args.block_mask not in ("none", "full"):
-        ap.error("--block-mask takes none, full or frame:W")
+    elif args.block_mask.startswith("topp:"):
+        top_p = float(args.block_mask.split(":", 1)[1])
+        if not 0.0 < top_p <= 1.0:
+            ap.error("--block-mask topp:P needs P in (0, 1]")
+        if args.key_mask != "none":
+            ap.error("--block-mask topp:P takes no key mask")
+    elif args.block_mask not in ("none", "full", "full4d"):
+        ap.error("--block-mask takes none, full, full4d, frame:W or topp:P")
     span = None
     if args.row_bounds.startswith("frame:"):
         back, ahead = args.row_bounds.split(":", 1)[1].split(",")
@@ -214,7 +226,24 @@ def main():
                 (torch.arange(Sk, device=dev) < live).expand(B, Sk))
         mk = {"key_mask": km}
         note = ""
-        if args.block_mask != "none":
+        if top_p is not None:
+            def select_pack():
+                return ops.pack_head_block_mask(
+                    ops.select_block_mask(q, k, top_p), B, H, S, Sk)
+
+            bm = select_pack()
+            prep = timeit(select_pack)
+            mk = {"block_mask": bm}
+            note = (f"  density {bm.block.float().mean().item():.4f}  "
+                    f"select+pack {prep*1e3:.3f} ms")
+        elif args.block_mask == "full4d":
+            # the per-head kernels on the pattern of `full`: their price
+            nq, nk = ops.reference.block_mask_shape(S, Sk)
+            block = torch.ones(1, 1, nq, nk, dtype=torch.bool, device=dev)
+            mk = {"block_mask": ops.pack_head_block_mask(block, B, H, S, Sk,
+                                                         km)}
+            note = "  density 1.0000"
+        elif args.block_mask != "none":
             nq, nk = ops.reference.block_mask_shape(S, Sk)
             block = (torch.ones(nq, nk, dtype=torch.bool, device=dev)
                      if window is None else ops.frame_window_block_mask(
